@@ -2,6 +2,7 @@
 """Batched JPEG decode benchmark (BASELINE.json metric: MPixels/s decoded, images/s, % HBM roofline).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5|c1] [--batch B]
+                    [--dump-outputs DIR] [--full]
 
 One step = one pass of the decode path (host header parse + plan, RST scan, Huffman, IDCT/colour)
 over one batch of synthetic JPEGs whose bytes are already resident in HBM; RGB stays in HBM.
@@ -10,7 +11,14 @@ images sharded by rank (weak scaling: each rank decodes its own batch of B image
 config 4 = 8 x config 2; mixed batches are balanced by estimated entropy-coded bytes), no
 collective on the data path; one all-gather of per-rank counters at the end (RCCL over xGMI).
 
-Rank 0 prints one JSON line (contract in the task statement) with, besides the contract keys:
+A plain run sets up, warms up, times the K steps and prints the line: the headline figures
+(value, ms_per_step, images/s, bytes/s), the workload, the shards, the per-rank host phase times of
+the timed steps and the device-memory high-water marks.  --dump-outputs DIR also writes what the
+last timed step left in HBM (dump_outputs below).  Everything that takes runs of its own (the
+bit-exactness spot check against the oracle, the serialized per-kernel pass and its rooflines, the
+copy peak, the H2D-inclusive legs, the CPU baselines) is done with --full only.
+
+With --full rank 0's JSON line (contract in the task statement) has, besides the contract keys:
   roofline      the dominant kernel's algorithmic bytes / its hipEvent-measured average launch time
                 against the 8 TB/s HBM peak, the same against an in-run copy-kernel peak (the
                 library's 16-byte-per-lane copy, jd_test_copy_peak), its HBM traffic and VALU issue
@@ -673,6 +681,37 @@ def ref_sweep(dec, datas, hosts, hdrs, in_ptrs, rgb_bufs, out_offs, dev, reps: i
     return out
 
 
+DUMP_SAMPLE = 4 << 20  # RGB bytes sampled by --dump-outputs (16 MB as float32)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path: str, rgb, out_offs, hdrs, results, dev, suffix: str = ""):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 .npy:
+      results<suffix>.npy     [images, 3]: jd_result status, width, height of every image
+      rgb_sample<suffix>.npy  the decoded RGB bytes at DUMP_SAMPLE positions drawn once (seeded, so
+                              the same positions in every run and build) from the batch's pixel
+                              bytes in image order, or every byte when the batch has fewer; the
+                              alignment gaps between images in the output buffer are never read.
+    The inputs are seeded too, so two builds run with the same arguments compare file for file."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    sizes = np.array([h.width * h.height * 3 for h in hdrs], np.int64)
+    ends = np.cumsum(sizes)
+    valid = int(ends[-1])
+    if valid <= DUMP_SAMPLE:
+        pos = np.arange(valid, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, valid, DUMP_SAMPLE, dtype=np.int64))
+    img = np.searchsorted(ends, pos, side="right")
+    off = np.asarray(out_offs, np.int64)[img] + pos - (ends[img] - sizes[img])
+    sample = rgb[torch.from_numpy(off).to(dev)].to(torch.float32).cpu().numpy()
+    np.save(os.path.join(path, f"rgb_sample{suffix}.npy"), sample)
+    np.save(os.path.join(path, f"results{suffix}.npy"),
+            np.array([[r.status, r.width, r.height] for r in results], np.float32).reshape(-1, 3))
+
+
 # ---------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -688,12 +727,21 @@ def main():
                     help="ref444: print the reference's two published curves instead of the bench line: "
                          "throughput vs batch size (JPEG MB/s) and single-image latency per size, next to the "
                          "reference's own CPU decoder (oracle/_ref/ref_bench) on the same files")
-    ap.add_argument("--cpu-sample", type=int, default=1, help="1: time the CPU baselines, 0: skip")
-    ap.add_argument("--verify", type=int, default=1, help="check images {0, n/2, n-1} bit-exact vs the oracle")
-    ap.add_argument("--e2e-steps", type=int, default=24, help="steps of each H2D-inclusive leg (0: skip; the last batch's kernels after its DMA are ~6 ms of pipeline drain, so few steps understate the rate)")
-    ap.add_argument("--copy-peak", type=int, default=1, help="measure an in-run HBM copy peak")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a seeded sample of the RGB "
+                         "bytes and every image's status, width, height) as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the bit-exactness spot check against the "
+                         "oracle, the serialized per-kernel pass with its rooflines, the copy peak, the "
+                         "H2D-inclusive legs and the CPU baselines (the options below select among them)")
+    ap.add_argument("--cpu-sample", type=int, default=1, help="--full: 1: time the CPU baselines, 0: skip")
+    ap.add_argument("--verify", type=int, default=1,
+                    help="--full or --sweep: check images {0, n/2, n-1} bit-exact vs the oracle; 0 also lets "
+                         "failed decode statuses pass")
+    ap.add_argument("--e2e-steps", type=int, default=24, help="--full: steps of each H2D-inclusive leg (0: skip; the last batch's kernels after its DMA are ~6 ms of pipeline drain, so few steps understate the rate)")
+    ap.add_argument("--copy-peak", type=int, default=1, help="--full: measure an in-run HBM copy peak")
     ap.add_argument("--kernel-steps", type=int, default=3,
-                    help="serialized (non-overlapped) steps after the timed region for per-kernel times")
+                    help="--full: serialized (non-overlapped) steps after the timed region for per-kernel times")
     ap.add_argument("--path", default="auto", choices=["auto", "sync", "lanes", "full"],
                     help="entropy-decode path (auto: lanes for images with restart intervals)")
     ap.add_argument("--fancy", action="store_true",
@@ -703,6 +751,8 @@ def main():
                     help="one blocking jd_decode_batch per step instead of jd_decode_batch_async (which "
                          "parses and plans step k+1 on the host while the GPU decodes step k)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "c2f":
         args.fancy = True
     rc = maybe_launch(args)
@@ -775,7 +825,7 @@ def main():
 
     # correctness spot check against the oracle (outside the timed region): head, middle, tail
     verified = []
-    if args.verify:
+    if args.verify and (args.full or args.sweep):
         import jdoracle
 
         for i in sorted({0, n // 2, n - 1}):
@@ -815,20 +865,26 @@ def main():
         raise SystemExit("decode failed inside the timed region")
     st_overlap = dec.stats()
     host_ms_step = {k: v / args.steps for k, v in st_overlap["host_ms"].items()}
+    if args.dump_outputs:
+        last = (args.steps - 1) % nb
+        dump_outputs(args.dump_outputs, rgb_bufs[last], out_offs, hdrs, batches[last][1], dev,
+                     "" if world == 1 else f"_rank{rank}")
     # per-kernel times for the roofline from serialized batches (outside the timed region): in the
     # timed loop consecutive batches overlap on the slot streams, so a kernel's hipEvent span there
     # includes the other batch's kernels
-    dec.reset_stats()
-    for k in range(max(1, args.kernel_steps)):
-        dec.decode_prepared(batches[k % nb], pipelined=False)
-    st = dec.stats()
+    st = None
+    if args.full:
+        dec.reset_stats()
+        for k in range(max(1, args.kernel_steps)):
+            dec.decode_prepared(batches[k % nb], pipelined=False)
+        st = dec.stats()
 
     # PCIe-inclusive rate (not `value`): the JPEG bytes handed over in host memory, RGB to HBM;
     # pipelined like the timed loop (the host stages batch k+1 while the GPU decodes batch k), run
     # by every rank at once so a multi-GPU run shows the shared host's feed rate
     e2e = None
     e2e_ms = h2d_gbs = reg_ms = arena_ms = 0.0
-    if args.e2e_steps:
+    if args.full and args.e2e_steps:
         def e2e_leg(batches):
             """The pipelined timed loop over host-input batches: (seconds, library stats)."""
             for k in range(len(batches)):
@@ -913,12 +969,9 @@ def main():
 
     # rank 0's single-host measurements after the gather, at every world size (the others wait)
     extra = rank0_measurements(rank, world,
-                               copy_fn=(lambda: copy_peak_gbs(dec, dev)) if args.copy_peak else None,
-                               cpu_fn=(lambda: cpu_baseline(hosts, hdrs)) if args.cpu_sample else None)
+                               copy_fn=(lambda: copy_peak_gbs(dec, dev)) if args.full and args.copy_peak else None,
+                               cpu_fn=(lambda: cpu_baseline(hosts, hdrs)) if args.full and args.cpu_sample else None)
     if rank == 0:
-        kern = st["kernels"]
-        copy_gbs = extra["copy_peak"]
-        cpu = extra["cpu_baseline"]
         px_rank = float(sum(h.width * h.height for h in hdrs))
         res = {
             "metric": "MPixels/s decoded (and images/s) at 1/2/4/8 MI355X; % HBM roofline",
@@ -951,13 +1004,9 @@ def main():
             "images_per_s": tot_img / t_max,
             "jpeg_MB_per_s": tot_bytes / t_max / 1e6,
             "ecs_MB_per_s": tot_ecs / t_max / 1e6,
-            "roofline": roofline_block(kern, args.config, copy_gbs, args.kernel_steps, rocprof_averages(args.config)),
-            "kernel_rooflines": kernel_rooflines(kern, args.config),
-            "kernels_ms_per_step": {k: v["total_ms"] / max(1, v["launches"]) for k, v in kern.items()},
             "kernels_ms_per_step_overlapped": {k: v["total_ms"] / max(1, v["launches"])
                                                for k, v in st_overlap["kernels"].items()},
             "path_roofline_frac": ((ecs + 3 * pixels) / (t_max / args.steps) / 1e9) / HBM_PEAK_GBS,
-            "e2e_h2d": e2e,
             "per_rank": per_rank_table(allc, args.steps),
             "device_memory": {"decoder_pools_peak_GB": dec.device_bytes()[1] / 1e9,
                               "torch_peak_GB": torch.cuda.max_memory_allocated(dev) / 1e9,
@@ -966,10 +1015,20 @@ def main():
                               "retried_images_timed": st_overlap["retried_images"],
                               "note": "rank 0: the library's grow-only pools (two in-flight slots) and the "
                                       "bench's own input/output buffers"},
-            "cpu_baseline": cpu,
-            "verified_bit_exact": verified,
             "gen_s": t_gen,
+            "full": args.full,
         }
+        if args.full:
+            kern = st["kernels"]
+            res.update({
+                "roofline": roofline_block(kern, args.config, extra["copy_peak"], args.kernel_steps,
+                                           rocprof_averages(args.config)),
+                "kernel_rooflines": kernel_rooflines(kern, args.config),
+                "kernels_ms_per_step": {k: v["total_ms"] / max(1, v["launches"]) for k, v in kern.items()},
+                "e2e_h2d": e2e,
+                "cpu_baseline": extra["cpu_baseline"],
+                "verified_bit_exact": verified,
+            })
         print(json.dumps(res))
     dec.close()
     if world > 1:

@@ -6,7 +6,7 @@ out=$1; shift
 mkdir -p "$out"
 for spec in "$@"; do
   name=${spec%%:*}; envs=${spec#*:}
-  env $envs timeout -k 10 300 python bench.py --steps 20 --warmup 3 --cpu-sample 0 --e2e-steps 0 \
+  env $envs timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --cpu-sample 0 --e2e-steps 0 \
     --copy-peak 0 ${AB_ARGS:-} > "$out/$name.json" 2> "$out/$name.err" || { tail -20 "$out/$name.err"; exit 1; }
   python - "$out/$name.json" "$name" <<'PY'
 import json, sys

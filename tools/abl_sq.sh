@@ -11,7 +11,7 @@ for v in "$@"; do
   lib=$root/gpu-jpeg-decoder_amd/libjdamd_$v.so; [ "$v" = cur ] && lib=$root/gpu-jpeg-decoder_amd/libjdamd.so
   export JDAMD_LIB=$lib JDAMD_ALLOW_ABI_MISMATCH=1
   (cd "$out" && timeout -s KILL 180 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES SQ_INSTS_LDS SQ_INSTS_SALU -d "$v" -o p -f csv -- \
-     python3 "$root/bench.py" --config "$cfg" --steps 2 --warmup 1 --cpu-sample 0 --verify 0 --e2e-steps 0 --copy-peak 0 \
+     python3 "$root/bench.py" --full --config "$cfg" --steps 2 --warmup 1 --cpu-sample 0 --verify 0 --e2e-steps 0 --copy-peak 0 \
      --kernel-steps 1 --no-pipeline > "$v.log" 2>&1)
   echo "$v done"
 done

@@ -12,7 +12,7 @@ tail -2 $out/tests.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()"
 for c in $cfgs; do
   cpu=0; [ "${FULL:-0}" = 1 ] && cpu=1
-  timeout -k 10 400 python bench.py --config $c --cpu-sample $cpu > $out/$c.json 2> $out/$c.err
+  timeout -k 10 400 python bench.py --full --config $c --cpu-sample $cpu > $out/$c.json 2> $out/$c.err
   python3 - $out/$c.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -11,8 +11,8 @@ mkdir -p $out
 export TMPDIR=/tmp
 for c in $cfgs; do
   echo "== $c $(date +%T)"
-  timeout -k 10 300 python bench.py --config $c > $out/$c.json 2> $out/$c.err
+  timeout -k 10 300 python bench.py --full --config $c > $out/$c.json 2> $out/$c.err
   tail -c 400 $out/$c.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/${c}_stats -o run -f csv -- \
-    python3 bench.py --config $c --steps 5 --warmup 1 --cpu-sample 0 --verify 0 > $out/${c}_stats.log 2>&1
+    python3 bench.py --full --config $c --steps 5 --warmup 1 --cpu-sample 0 --verify 0 > $out/${c}_stats.log 2>&1
 done

@@ -10,7 +10,7 @@ for a in "$@"; do
   i=$((i+1))
   envs=(); rest=()
   for w in $a; do if [[ $w == *=* && ${#rest[@]} == 0 ]]; then envs+=("$w"); else rest+=("$w"); fi; done
-  timeout -k 10 400 env "${envs[@]}" python bench.py --cpu-sample 0 "${rest[@]}" > $out/b$i.json 2> $out/b$i.err || { tail -5 $out/b$i.err; exit 1; }
+  timeout -k 10 400 env "${envs[@]}" python bench.py --full --cpu-sample 0 "${rest[@]}" > $out/b$i.json 2> $out/b$i.err || { tail -5 $out/b$i.err; exit 1; }
   python3 - $out/b$i.json "$a" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -15,14 +15,14 @@ root=$PWD
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-short="--steps 2 --warmup 1 --cpu-sample 0 --verify 0 --e2e-steps 0 --copy-peak 0 --kernel-steps 1 --no-pipeline"
+short="--full --steps 2 --warmup 1 --cpu-sample 0 --verify 0 --e2e-steps 0 --copy-peak 0 --kernel-steps 1 --no-pipeline"
 for c in $cfgs; do
   echo "== $c $(date +%T)"
   cpu=0; [ "$c" = c2 ] && cpu=1; [ "$c" = c1 ] && cpu=1
-  timeout -k 10 400 python bench.py --config $c --cpu-sample $cpu > $out/$c.json 2> $out/$c.err
+  timeout -k 10 400 python bench.py --full --config $c --cpu-sample $cpu > $out/$c.json 2> $out/$c.err
   tail -c 300 $out/$c.json; echo
   (cd $out && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d ${c}_stats -o run -f csv -- \
-     python3 $root/bench.py --config $c --steps 5 --warmup 1 --cpu-sample 0 --verify 0 --e2e-steps 0 \
+     python3 $root/bench.py --full --config $c --steps 5 --warmup 1 --cpu-sample 0 --verify 0 --e2e-steps 0 \
      --copy-peak 0 --kernel-steps 1 --no-pipeline > ${c}_stats.log 2>&1)
   (cd $out && timeout -s KILL 180 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d ${c}_fetch -o p -f csv -- \
      python3 $root/bench.py --config $c $short > ${c}_fetch.log 2>&1)

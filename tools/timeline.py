@@ -1,6 +1,6 @@
 """Kernel timeline of a pipelined bench run from a rocprofv3 kernel trace.
 
-    rocprofv3 --kernel-trace -d trace -o run -f csv -- python3 bench.py --steps 12 --warmup 3 \\
+    rocprofv3 --kernel-trace -d trace -o run -f csv -- python3 bench.py --full --steps 12 --warmup 3 \\
         --cpu-sample 0 --verify 0 --e2e-steps 0 --copy-peak 0 --kernel-steps 0
     python tools/timeline.py trace/run_kernel_trace.csv [batches]
 

@@ -19,7 +19,7 @@ for spec in "$@"; do
   t=$(echo "$spec" | tr '@,=/' '____')
   for kv in ${envs//,/ }; do export "$kv"; done
   (cd /tmp && JDAMD_LIB=$lib JDAMD_ALLOW_ABI_MISMATCH=1 timeout -k 10 300 rocprofv3 --kernel-trace -d "$out/$t" -o t -f csv -- \
-     python3 "$root/bench.py" --steps 12 --warmup 3 --cpu-sample 0 --verify 0 --e2e-steps 0 --copy-peak 0 \
+     python3 "$root/bench.py" --full --steps 12 --warmup 3 --cpu-sample 0 --verify 0 --e2e-steps 0 --copy-peak 0 \
      --kernel-steps 0 ${TRACE_ARGS:-} > "$out/$t.log" 2>&1)
   for kv in ${envs//,/ }; do unset "${kv%%=*}"; done
   python3 tools/timeline.py "$(find "$out/$t" -name '*kernel_trace.csv' | head -1)" 4 > "$out/$t.txt"
