@@ -3685,9 +3685,10 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
     const bool have = L.have;
     // dequantise in zig-zag order (24-bit multiplies: |coef| < 2^15, q < 2^16) into natural
     // positions (a compile-time permutation of registers), then the IDCT in registers
-    //    The fast IDCT form needs every dequantised coefficient within +-2^16: an AC coefficient
-    //    c is when |c| <= 2^(k-1) with 2^(k-1) * (largest quant step) < 2^16 (host: im.qmask),
-    //    i.e. when bits k-1..15 of c all equal its sign: c ^ (c << 1) has bits k..15 clear.
+    //    The fast IDCT form needs every dequantised coefficient to fit int16: an AC coefficient
+    //    c does when -2^(k-1) <= c < 2^(k-1) with 2^(k-1) * (largest quant step) < 2^15 (host:
+    //    im.qmask), i.e. when bits k-1..15 of c all equal its sign: c ^ (c << 1) has bits k..15
+    //    clear.  k = 0 (a step of 2^15 or more): only c = 0 passes.
     // the lane's staging row as 8 quads (swizzled: quad q at base ^ 16 q); lanes without a block
     // read row 0 (their results are never used)
     const uint8_t* s_bytes = reinterpret_cast<const uint8_t*>(s_buf);
@@ -3817,7 +3818,9 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
     const uint32_t W = im.width, H = im.height, W3 = 3u * W;  // W3 < 2^18
     const uint32_t x_tile = m0 << lg_mw, y_tile = r0 << lg_mh;
     const uint32_t shx1 = TM_::shx(im, 1), shy1 = TM_::shy(im, 1), shx2 = TM_::shx(im, 2), shy2 = TM_::shy(im, 2);
-    const uint32_t cmode = nc == 1 ? 3u : (shx1 == shx2 ? shx1 : 4u);
+    // (luma below the maximum factor, e.g. Y 1x1 with 2x1 chroma: the generic instance only)
+    const uint32_t shx0 = TM_::shx(im, 0), shy0 = TM_::shy(im, 0);
+    const uint32_t cmode = nc == 1 ? 3u : ((shx1 == shx2 && (shx0 | shy0) == 0u) ? shx1 : 4u);
     const bool pair = cmode <= 2u && shy1 >= 1u && shy2 >= 1u;  // wave-uniform; th is even then
     const uint32_t rows = pair ? 2u : 1u, ngy = th / rows;
     uint8_t* out = reinterpret_cast<uint8_t*>(im.rgb);
@@ -3836,7 +3839,7 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
         const uint32_t py = gy * rows, gx = gc << 3;
         const uint32_t y = y_tile + py, x = x_tile + gx;
         if (y >= H || x >= W) continue;
-        const uint32_t yoff = pbase[0] + py * ppitch[0] + gx;
+        const uint32_t yoff = pbase[0] + (py >> shy0) * ppitch[0] + (gx >> shx0);
         const uint32_t cboff = pbase[1] + (py >> shy1) * ppitch[1] + (gx >> shx1);
         const uint32_t croff = pbase[2] + (py >> shy2) * ppitch[2] + (gx >> shx2);
         uint32_t w0[6], w1[6];
@@ -3871,14 +3874,15 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
                     }
                 }
             }
-        } else {  // grayscale, or chroma planes with different horizontal factors: per pixel
+        } else {  // grayscale, a subsampled Y, or chroma planes with different horizontal factors: per pixel
             int Y0[8];
-            load_plane<0>(s_pl, yoff, Y0);
             uint32_t rgb[8][3];
             if (cmode == 3u) {
+                load_plane<0>(s_pl, yoff, Y0);
                 colour8<3>(Y0, s_pl, cboff, croff, rgb);
             } else {
                 int Cb[8], Cr[8];
+                load8_samples(s_pl, yoff, shx0, Y0);
                 load8_samples(s_pl, cboff, shx1, Cb);
                 load8_samples(s_pl, croff, shx2, Cr);
 #pragma unroll
