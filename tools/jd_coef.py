@@ -2,7 +2,10 @@
 
 build() writes a valid baseline stream from quantised coefficients chosen by the caller, for any
 sampling layout the parser accepts (factors 1, 2, 4; at most 10 blocks per MCU), 8- or 16-bit
-quantisation tables and any restart interval.  reference() computes the RGB of the same
+quantisation tables and any restart interval; with the Annex K.3 Huffman tables below, or with
+tables given per component (huff=: any DHT ids and packing, DC sizes to 16, AC sizes to 15;
+canonical() makes a table from code lengths), from coefficients or, for the sequences no
+coefficients produce, from the symbols themselves (symbols=, coefs_of_symbols()).  reference() computes the RGB of the same
 coefficients directly: dequantise, IDCT per block (jdoracle.idct, pinned to the reference decoder
 by the ground-truth fixtures), planes, replicate upsampling, colour in float64 / float32 as the
 reference rounds.  It reads no bitstream and shares no layout or colour code with
@@ -60,10 +63,6 @@ def _codes(bits, vals):
     return out
 
 
-_DC = _codes(DC_BITS, DC_VALS)
-_AC = (_codes(AC_LUMA_BITS, AC_LUMA_VALS), _codes(AC_CHROMA_BITS, AC_CHROMA_VALS))
-
-
 def grid(width, height, factors):
     """(hmax, vmax, mcux, mcuy) of a frame; a single component is one block per MCU."""
     if len(factors) == 1:
@@ -86,8 +85,10 @@ class _Bits:
         self.out = bytearray()
         self.acc = 0
         self.n = 0
+        self.total = 0  # bits put, padding included
 
     def put(self, value, length):
+        self.total += length
         self.acc = (self.acc << length) | (value & ((1 << length) - 1))
         self.n += length
         while self.n >= 8:
@@ -108,15 +109,42 @@ def _magnitude(v):
     return size, (v if v >= 0 else v + (1 << size) - 1)
 
 
-def _put_block(bw, zz, pred, ac):
+def canonical(lengths):
+    """(bits[16], vals) of the canonical code with the given symbol -> code length (1..16); symbols
+    of one length keep the mapping's order.  Rejects what a DHT segment cannot carry or Annex C
+    forbids: an over-subscribed set, one that uses the all-ones code of its longest length (a
+    complete set does), more than 255 codes of one length (a DHT count is one byte)."""
+    bits = [0] * 16
+    for sym, length in lengths.items():
+        if not (0 <= sym <= 255 and 1 <= length <= 16):
+            raise ValueError(f"symbol {sym} / length {length} out of range")
+        bits[length - 1] += 1
+    if not lengths:
+        raise ValueError("empty code")
+    if max(bits) > 255:
+        raise ValueError("more than 255 codes of one length")
+    kraft = sum(n << (16 - l) for l, n in enumerate(bits, start=1))
+    if kraft > 1 << 16:
+        raise ValueError("over-subscribed code lengths")
+    if kraft == 1 << 16:
+        raise ValueError("the all-ones code of the longest length is in use")
+    vals = [sym for sym, _ in sorted(lengths.items(), key=lambda kv: kv[1])]  # stable: mapping order
+    return bits, vals
+
+
+def scan_blocks(width, height, factors):
+    """(component, block row, block column) of every block in scan order (MCU by MCU)."""
+    _, _, mcux, mcuy = grid(width, height, factors)
+    eff = [(1, 1)] if len(factors) == 1 else list(factors)
+    return [(c, my * v + by, mx * h + bx) for my in range(mcuy) for mx in range(mcux)
+            for c, (h, v) in enumerate(eff) for by in range(v) for bx in range(h)]
+
+
+def symbols_of_block(zz, pred):
+    """Coefficients -> symbols: ((size, diff), [(run/size byte, value), ...]) of one block, as an
+    encoder writes them (ZRL for runs beyond 15, EOB unless position 63 is non-zero)."""
     diff = int(zz[0]) - pred
-    size, bits = _magnitude(diff)
-    if size > 12:
-        raise ValueError(f"DC difference {diff} beyond the DC table")
-    code, length = _DC[size]
-    bw.put(code, length)
-    if size:
-        bw.put(bits, size)
+    acs = []
     run = 0
     nz = np.flatnonzero(zz[1:])
     last = int(nz[-1]) + 1 if nz.size else 0
@@ -126,35 +154,130 @@ def _put_block(bw, zz, pred, ac):
             run += 1
             continue
         while run > 15:
-            bw.put(*ac[0xF0])
+            acs.append((0xF0, 0))
             run -= 16
-        size, bits = _magnitude(v)
-        if size > 10:
-            raise ValueError(f"AC coefficient {v} beyond the AC tables")
-        bw.put(*ac[(run << 4) | size])
-        bw.put(bits, size)
+        if abs(v) > 32767:
+            raise ValueError(f"AC coefficient {v} beyond size 15")
+        acs.append(((run << 4) | int(abs(v)).bit_length(), v))
         run = 0
     if last < 63:
-        bw.put(*ac[0x00])
+        acs.append((0x00, 0))
+    return (int(abs(diff)).bit_length(), diff), acs
+
+
+def coefs_of_symbols(dc, acs, pred):
+    """Symbols -> the 64 coefficients (zig-zag, absolute DC) the reference decodes from them
+    (parser.cpp:114-134): k += run; read the magnitude; store it only if k < 64; k++; the block
+    ends at EOB or at k >= 64.  Symbols after the block's end are an error of the caller."""
+    zz = np.zeros(64, np.int32)
+    zz[0] = pred + dc[1]
+    k = 1
+    for i, (rs, value) in enumerate(acs):
+        if k >= 64:
+            raise ValueError("symbols after the block's end")
+        if rs == 0:
+            if i != len(acs) - 1:
+                raise ValueError("symbols after EOB")
+            return zz
+        k += rs >> 4
+        if k < 64:
+            zz[k] = value if rs & 15 else 0
+            k += 1
+    if k < 64:
+        raise ValueError("block neither ends with EOB nor reaches position 63")
+    return zz
+
+
+def coefs_of_scan(width, height, factors, symbols, restart=0):
+    """The coefficient arrays (coef_shapes) that a scan's symbols decode to, block by block through
+    coefs_of_symbols(), the DC prediction reset at every restart interval."""
+    nc = len(factors)
+    coefs = [np.zeros(s, np.int32) for s in coef_shapes(width, height, factors)]
+    bpm = sum(h * v for h, v in ([(1, 1)] if nc == 1 else factors))
+    pred = [0] * nc
+    for n, (c, row, col) in enumerate(scan_blocks(width, height, factors)):
+        if restart and n % (restart * bpm) == 0:
+            pred = [0] * nc
+        coefs[c][row, col] = coefs_of_symbols(*symbols[n], pred[c])
+        pred[c] = int(coefs[c][row, col, 0])
+    return coefs
+
+
+def _put_symbols(bw, dc, acs, dc_codes, ac_codes):
+    """Symbols -> bits.  The size limits are the tables': a symbol they lack is an error."""
+    size, diff = dc
+    if size != int(abs(diff)).bit_length() or size > 16:
+        raise ValueError(f"DC difference {diff} is not of size {size}")
+    if size not in dc_codes:
+        raise ValueError(f"DC difference {diff} (size {size}) beyond the DC table")
+    bw.put(*dc_codes[size])
+    if size:
+        bw.put(_magnitude(diff)[1], size)
+    for rs, value in acs:
+        if rs not in ac_codes:
+            raise ValueError(f"AC symbol {rs:#04x} (value {value}) beyond the AC table")
+        bw.put(*ac_codes[rs])
+        size = rs & 15
+        if size:
+            if size != int(abs(value)).bit_length():
+                raise ValueError(f"AC value {value} is not of size {size}")
+            bw.put(_magnitude(value)[1], size)
+
+
+_ANNEX_K = {"tables": [((DC_BITS, DC_VALS), (AC_LUMA_BITS, AC_LUMA_VALS))] +
+                      [((DC_BITS, DC_VALS), (AC_CHROMA_BITS, AC_CHROMA_VALS))] * 2,
+            "ids": [(0, 0), (0, 1), (0, 1)], "packing": "each"}
+
+
+def _dht_segments(huff, nc):
+    """The DHT segments of a table set (see build()): (before SOF, after SOF)."""
+    flags = set(huff.get("packing", "each").split("+"))
+    assert flags <= {"each", "one", "twice", "before_sof"} and not {"each", "one"} <= flags
+    defs = {}  # (class, id) -> (bits, vals), in order of first use
+    for c in range(nc):
+        for tc in (0, 1):
+            spec, th = huff["tables"][c][tc], huff["ids"][c][tc]
+            bits, vals = [int(x) for x in spec[0]], [int(x) for x in spec[1]]
+            assert 0 <= th <= 3 and len(bits) == 16 and sum(bits) == len(vals) and max(bits) <= 255
+            assert defs.setdefault((tc, th), (bits, vals)) == (bits, vals), "one id, two tables"
+    body = [bytes([(tc << 4) | th]) + bytes(bits) + bytes(vals) for (tc, th), (bits, vals) in defs.items()]
+    if "twice" in flags:  # every id first defined with another table (the later definition wins)
+        decoy = {0: (DC_BITS, DC_VALS), 1: (AC_LUMA_BITS, AC_LUMA_VALS)}
+        body = [bytes([(tc << 4) | th]) + bytes(decoy[tc][0]) + bytes(decoy[tc][1]) for tc, th in defs] + body
+    segs = [_segment(0xC4, b"".join(body))] if "one" in flags else [_segment(0xC4, b) for b in body]
+    return (b"".join(segs), b"") if "before_sof" in flags else (b"", b"".join(segs))
 
 
 def _segment(marker, payload):
     return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + bytes(payload)
 
 
-def build(width, height, factors, coefs, qtabs, tq=None, restart=0, comp_ids=(1, 2, 3)):
+def build(width, height, factors, coefs, qtabs, tq=None, restart=0, comp_ids=(1, 2, 3), huff=None, symbols=None,
+          info=None):
     """Baseline JPEG bytes.  factors: (h, v) per component; coefs[c]: int [block_rows, block_cols,
     64], zig-zag order, absolute DC, before dequantisation, on the padded MCU grid (coef_shapes);
     qtabs: 64-entry tables in zig-zag order (an entry above 255 makes the table 16-bit); tq: table
     index per component (default: 0 for the first, the last table for the others); restart: MCUs
-    per restart interval (0: none)."""
+    per restart interval (0: none).
+    huff: None for the Annex K set above, else {"tables": per component ((bits, vals) DC, (bits,
+    vals) AC), "ids": per component (Td, Ta), the DHT ids 0..3 the tables are written under and the
+    SOS selects, "packing": "each" (one DHT segment per table) or "one" (all in one segment),
+    optionally with "+twice" (every id defined first with another table) and "+before_sof"}.
+    symbols: instead of coefs (None), per block in scan order ((size, diff), [(run/size byte,
+    value), ...]), written as given (coefs_of_symbols() says what they decode to).
+    info: a dict that receives "bits", the entropy-coded bits written (padding included)."""
     nc = len(factors)
-    assert nc in (1, 3) and len(coefs) == nc
+    assert nc in (1, 3) and (symbols is None) != (coefs is None)
+    nblocks = len(scan_blocks(width, height, factors))
+    if symbols is None:
+        assert len(coefs) == nc
+    else:
+        assert len(symbols) == nblocks
     if tq is None:
         tq = [0] + [len(qtabs) - 1] * (nc - 1)
     hmax, vmax, mcux, mcuy = grid(width, height, factors)
     eff = [(1, 1)] if nc == 1 else list(factors)  # a single-component scan is not interleaved
-    for c, shape in enumerate(coef_shapes(width, height, factors)):
+    for c, shape in enumerate(coef_shapes(width, height, factors) if symbols is None else []):
         assert tuple(coefs[c].shape) == shape, (c, coefs[c].shape, shape)
     out = bytearray(b"\xff\xd8")
     for t, q in enumerate(qtabs):
@@ -167,35 +290,36 @@ def build(width, height, factors, coefs, qtabs, tq=None, restart=0, comp_ids=(1,
     sof = bytes([8]) + height.to_bytes(2, "big") + width.to_bytes(2, "big") + bytes([nc])
     for c in range(nc):
         sof += bytes([comp_ids[c], (factors[c][0] << 4) | factors[c][1], tq[c]])
-    out += _segment(0xC0, sof)
-    out += _segment(0xC4, bytes([0x00]) + bytes(DC_BITS) + bytes(DC_VALS))
-    out += _segment(0xC4, bytes([0x10]) + bytes(AC_LUMA_BITS) + bytes(AC_LUMA_VALS))
-    if nc == 3:
-        out += _segment(0xC4, bytes([0x11]) + bytes(AC_CHROMA_BITS) + bytes(AC_CHROMA_VALS))
+    if huff is None:
+        huff = _ANNEX_K
+    dht_before, dht_after = _dht_segments(huff, nc)
+    out += dht_before + _segment(0xC0, sof) + dht_after
+    codes = [(_codes(*huff["tables"][c][0]), _codes(*huff["tables"][c][1])) for c in range(nc)]
     if restart:
         out += _segment(0xDD, int(restart).to_bytes(2, "big"))
     sos = bytes([nc])
     for c in range(nc):
-        sos += bytes([comp_ids[c], 0x00 if c == 0 else 0x01])
+        sos += bytes([comp_ids[c], (huff["ids"][c][0] << 4) | huff["ids"][c][1]])
     out += _segment(0xDA, sos + bytes([0, 63, 0]))
     bw = _Bits()
     pred = [0] * nc
     rst = 0
-    for m in range(mcux * mcuy):
-        if restart and m and m % restart == 0:
+    bpm = sum(h * v for h, v in eff)
+    for n, (c, row, col) in enumerate(scan_blocks(width, height, factors)):
+        if restart and n and n % (restart * bpm) == 0:
             bw.flush()
             bw.out += bytes([0xFF, 0xD0 + (rst & 7)])
             rst += 1
             pred = [0] * nc
-        my, mx = divmod(m, mcux)
-        for c in range(nc):
-            h, v = eff[c]
-            for by in range(v):
-                for bx in range(h):
-                    zz = coefs[c][my * v + by, mx * h + bx]
-                    _put_block(bw, zz, pred[c], _AC[0 if c == 0 else 1])
-                    pred[c] = int(zz[0])
+        if symbols is None:
+            dc, acs = symbols_of_block(coefs[c][row, col], pred[c])
+        else:
+            dc, acs = symbols[n]
+        _put_symbols(bw, dc, acs, *codes[c])
+        pred[c] += dc[1]
     bw.flush()
+    if info is not None:
+        info["bits"] = bw.total
     out += bw.out
     out += b"\xff\xd9"
     return bytes(out)

@@ -12,6 +12,11 @@
 // restart_interval ecs_offset plan mode tiles_x tiles_y rw_div.  `plan` is 0, or JD_ERR_CORRUPT for a table
 // the LUT builder rejects, or JD_ERR_CAPACITY for an image beyond the 32-bit entry offsets.
 // Any sanitizer finding aborts the process with a non-zero status (-fno-sanitize-recover=all).
+//
+// `--luts records.bin` prints instead, per record, the parse status and component count, then per
+// component its DC and its AC table as build_lut made them: one line "lut <component> <0 DC | 1 AC>
+// <build_lut's result>" followed by the 2 * kLutSize fast[] words, the 20 lim[] and the 20 base[]
+// words in hex (tests/test_huff_ref.py checks every one against a model of jd_internal.hpp).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -49,12 +54,27 @@ static int plan_one(const uint8_t* buf, size_t len, const ParsedJpeg& pj, ImgDes
     return 0;
 }
 
+static void print_luts(const ParsedJpeg& pj) {
+    HuffLut* lut = new HuffLut;
+    for (int c = 0; c < pj.hdr.ncomp; c++)
+        for (int ac = 0; ac < 2; ac++) {
+            const bool ok = build_lut(ac ? pj.ac[pj.ta[c]] : pj.dc[pj.td[c]], !ac, lut);
+            printf("lut %d %d %d", c, ac, int(ok));
+            for (int i = 0; i < 2 * kLutSize; i++) printf(" %x", lut->fast[i]);
+            for (int i = 0; i < 20; i++) printf(" %x", lut->lim[i]);
+            for (int i = 0; i < 20; i++) printf(" %x", uint32_t(lut->base[i]));
+            printf("\n");
+        }
+    delete lut;
+}
+
 int main(int argc, char** argv) {
-    if (argc < 2) {
-        fprintf(stderr, "usage: %s records.bin\n", argv[0]);
+    const bool luts = argc >= 3 && !strcmp(argv[1], "--luts");
+    if (argc < 2 || (argc >= 3 && !luts)) {
+        fprintf(stderr, "usage: %s [--luts] records.bin\n", argv[0]);
         return 2;
     }
-    FILE* f = fopen(argv[1], "rb");
+    FILE* f = fopen(argv[luts ? 2 : 1], "rb");
     if (!f) return 2;
     std::vector<uint8_t> all;
     uint8_t tmp[1 << 16];
@@ -72,7 +92,10 @@ int main(int argc, char** argv) {
         off += len;
         ParsedJpeg* pj = new ParsedJpeg();
         const jd_status st = parse_jpeg(buf, len, pj);
-        if (st != JD_OK) {
+        if (luts) {
+            printf("%d %d\n", int(st), st == JD_OK ? pj->hdr.ncomp : 0);
+            if (st == JD_OK) print_luts(*pj);
+        } else if (st != JD_OK) {
             printf("%d\n", int(st));
         } else {
             const jd_header& h = pj->hdr;
