@@ -106,7 +106,7 @@ struct TableSet {
 // Per image of a batch (device array, one entry per decodable image).
 struct alignas(16) ImgDesc {
     uint64_t jpeg;     // device address of the file bytes
-    uint64_t rgb;      // device address of the H*W*3 uint8 output
+    uint64_t rgb;      // device address of the uint8 output (H*W*3 bytes, H*W for kFmtGray)
     uint64_t comp;     // device address of this image's un-stuffed entropy-coded data
     uint32_t len;      // file length in bytes
     uint32_t ecs_off;  // first ECS byte
@@ -278,6 +278,11 @@ constexpr int kTileMaxBlocks = JD_TILE_BLOCKS;   // blocks per IDCT/colour tile 
 constexpr uint32_t kFancyW = 128, kFancyH = 16, kFancyBands = JD_FANCY_BANDS;
 constexpr uint32_t kFancyRowsPerWg = kFancyH * kFancyBands;
 
+// Output format of a batch (BatchDev::out_fmt; jd.h JD_FLAG_OUT_*): a compile-time parameter of the
+// colour/store stage of k_idct_color, k_idct_color_exact and k_colour_fancy.  kFmtBgr and kFmtPlanar
+// are bits (kFmtPlanar | kFmtBgr: planes in B, G, R order); kFmtGray stands alone.
+constexpr uint32_t kFmtRgb = 0, kFmtBgr = 1, kFmtPlanar = 2, kFmtGray = 4;
+
 // Per-image status bits written by kernels (atomicOr); host maps them to jd_status.
 constexpr uint32_t kStCorrupt = 1u;     // bad code / overrun / DC range
 constexpr uint32_t kStRstMissing = 2u;  // fewer RST markers than intervals
@@ -382,6 +387,7 @@ struct BatchDev {
     uint32_t mode_off[4], mode_cnt[4], mode_max_tiles[4];
     unsigned long long* stamps;   // diagnostic builds (JD_STAMP): 8 s_memtime stamps per IDCT tile, else null
     uint32_t fancy;
+    uint32_t out_fmt;             // kFmt*: which instance of the colour kernels the launcher picks
     uint32_t max_fancy_wgs;       // k_colour_fancy bands per image: x in bits 0..15, y in 16..31
     uint32_t fix_round_cap;       // diagnostics (JD_FIX_ROUND_CAP): k_chain_big gives up (corrupt) after this many rounds; 0: never
     uint32_t skip_redo;           // diagnostics (JD_SKIP_REDO): no k_redo (the speculative starts stay as k_piece left them)

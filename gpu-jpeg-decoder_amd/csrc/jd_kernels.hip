@@ -18,7 +18,8 @@
 //   k_dc_sum / k_dc_scan   DC predictors at every IDCT tile's first block
 //   k_idct_color   one wave per tile (a run of <= 64 blocks of one MCU row): DC prediction,
 //                  dequantisation, integer IDCT in registers, replicate chroma upsampling and
-//                  YCbCr->RGB -> uint8 HWC; k_idct_color_exact takes the (never seen) tiles whose
+//                  YCbCr->RGB -> uint8 HWC (or the batch's output format, a template parameter of the
+//                  colour/store stage: planar, BGR, gray); k_idct_color_exact takes the (never seen) tiles whose
 //                  coefficients are beyond the fast IDCT form's range
 //   k_colour_fancy (JD_FLAG_FANCY_UPSAMPLING only) libjpeg's triangular upsampling + colour
 //
@@ -3297,7 +3298,8 @@ __device__ __forceinline__ void row_rgb_il(const uint4& Yq, const uint32_t (&A)[
 // The term words of row_rgb_il for the 8 >> SH chroma samples under 8 pixels (word u = pixels 2u,
 // 2u + 1): R and B straight from the high halves of their multiply-add sums (rb_pair), G's low half.
 // Returns the mask of samples (bit u) whose G needs the reference's double-precision path.
-template <int SH>
+// BGR: the R and B inputs exchanged, so the same adds write (b0 g0) (r0 b1) (g1 r1).
+template <int SH, bool BGR = false>
 __device__ __forceinline__ uint32_t terms_il(const int16_t* s_pl, uint32_t cboff, uint32_t croff, uint32_t (&A)[4],
                                              uint32_t (&B)[4], uint32_t (&C)[4]) {
     constexpr int NU = 8 >> SH;
@@ -3310,8 +3312,10 @@ __device__ __forceinline__ uint32_t terms_il(const int16_t* s_pl, uint32_t cboff
     for (int u = 0; u < NU; u++) {
         const ChromaTerms t = chroma_terms(cb[u], cr[u]);
         ex |= t.exact ? (1u << u) : 0u;
-        xr[u] = uint32_t(mad24(cr[u], 91881, 128 << 16));
-        xb[u] = uint32_t(mad24(cb[u], 116130, (128 << 16) + 64));
+        const uint32_t r = uint32_t(mad24(cr[u], 91881, 128 << 16));
+        const uint32_t bl = uint32_t(mad24(cb[u], 116130, (128 << 16) + 64));
+        xr[u] = BGR ? bl : r;
+        xb[u] = BGR ? r : bl;
         tg[u] = uint32_t(t.g);
     }
 #pragma unroll
@@ -3385,14 +3389,17 @@ __device__ __forceinline__ void rgb4_il(const uint2& Yq, const uint32_t (&A)[2],
     for (int k = 0; k < 3; k++) w[k] = sat_hi(sat_lo(P[2 * k]), P[2 * k + 1]);
 }
 // term words (terms_il) of pixels 2w, 2w + 1 on chroma samples a0, a1
+template <bool BGR = false>
 __device__ __forceinline__ void term_words_of(const ChromaTerms& t0, int cb0, int cr0, const ChromaTerms& t1, int cb1,
                                               int cr1, uint32_t& A, uint32_t& B, uint32_t& C) {
-    const uint32_t xr0 = uint32_t(mad24(cr0, 91881, 128 << 16)), xr1 = uint32_t(mad24(cr1, 91881, 128 << 16));
-    const uint32_t xb0 = uint32_t(mad24(cb0, 116130, (128 << 16) + 64)), xb1 = uint32_t(mad24(cb1, 116130, (128 << 16) + 64));
+    const uint32_t r0 = uint32_t(mad24(cr0, 91881, 128 << 16)), r1 = uint32_t(mad24(cr1, 91881, 128 << 16));
+    const uint32_t b0 = uint32_t(mad24(cb0, 116130, (128 << 16) + 64)), b1 = uint32_t(mad24(cb1, 116130, (128 << 16) + 64));
+    const uint32_t xr0 = BGR ? b0 : r0, xr1 = BGR ? b1 : r1, xb0 = BGR ? r0 : b0, xb1 = BGR ? r1 : b1;
     A = __builtin_amdgcn_perm(uint32_t(t0.g), xr0, 0x05040302u);
     B = __builtin_amdgcn_perm(xr1, xb0, 0x07060302u);
     C = __builtin_amdgcn_perm(xb1, uint32_t(t1.g), 0x07060100u);
 }
+template <bool BGR = false>
 __device__ __forceinline__ void colour4x2(const int16_t* s_pl, uint32_t yoff, uint32_t ypitch, uint32_t cboff,
                                           uint32_t croff, uint32_t (&w0)[3], uint32_t (&w1)[3]) {
     const uint32_t cbw = *reinterpret_cast<const uint32_t*>(s_pl + cboff);
@@ -3401,8 +3408,8 @@ __device__ __forceinline__ void colour4x2(const int16_t* s_pl, uint32_t yoff, ui
     const int cr[2] = {int(int16_t(crw & 0xFFFFu)), int32_t(crw) >> 16};
     const ChromaTerms t0 = chroma_terms(cb[0], cr[0]), t1 = chroma_terms(cb[1], cr[1]);
     uint32_t A[2], B[2], C[2];  // word u = pixels 2u, 2u + 1 on sample u
-    term_words_of(t0, cb[0], cr[0], t0, cb[0], cr[0], A[0], B[0], C[0]);
-    term_words_of(t1, cb[1], cr[1], t1, cb[1], cr[1], A[1], B[1], C[1]);
+    term_words_of<BGR>(t0, cb[0], cr[0], t0, cb[0], cr[0], A[0], B[0], C[0]);
+    term_words_of<BGR>(t1, cb[1], cr[1], t1, cb[1], cr[1], A[1], B[1], C[1]);
     const uint32_t ex = (t0.exact ? 1u : 0u) | (t1.exact ? 2u : 0u);
     const uint2 Y0 = *reinterpret_cast<const uint2*>(s_pl + yoff), Y1 = *reinterpret_cast<const uint2*>(s_pl + yoff + ypitch);
     rgb4_il(Y0, A, B, C, w0);
@@ -3415,6 +3422,7 @@ __device__ __forceinline__ void colour4x2(const int16_t* s_pl, uint32_t yoff, ui
 
 // The 4:4:4 tail step: 4 pixels of one row, one chroma sample each.  A 4:4:4 tile of 20 MCUs has
 // 160 8-pixel groups, two and a half lane-steps: the last half step is done as 64 4-pixel halves.
+template <bool BGR = false>
 __device__ __forceinline__ void colour4x1(const int16_t* s_pl, uint32_t yoff, uint32_t cboff, uint32_t croff,
                                           uint32_t (&w)[3]) {
     const uint2 cbq = *reinterpret_cast<const uint2*>(s_pl + cboff);
@@ -3429,8 +3437,8 @@ __device__ __forceinline__ void colour4x1(const int16_t* s_pl, uint32_t yoff, ui
         ex |= t[u].exact ? (1u << u) : 0u;
     }
     uint32_t A[2], B[2], C[2];  // word u = pixels 2u, 2u + 1 on samples 2u, 2u + 1
-    term_words_of(t[0], cb[0], cr[0], t[1], cb[1], cr[1], A[0], B[0], C[0]);
-    term_words_of(t[2], cb[2], cr[2], t[3], cb[3], cr[3], A[1], B[1], C[1]);
+    term_words_of<BGR>(t[0], cb[0], cr[0], t[1], cb[1], cr[1], A[0], B[0], C[0]);
+    term_words_of<BGR>(t[2], cb[2], cr[2], t[3], cb[3], cr[3], A[1], B[1], C[1]);
     const uint2 Y0 = *reinterpret_cast<const uint2*>(s_pl + yoff);
     rgb4_il(Y0, A, B, C, w);
     if (__any(ex != 0u)) {
@@ -3445,6 +3453,157 @@ __device__ __forceinline__ void colour4x1(const int16_t* s_pl, uint32_t yoff, ui
             }
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Planar and gray output (BatchDev::out_fmt): the colour of 8 pixels as two words per channel,
+// w[2 c], w[2 c + 1] = the 8 bytes of channel c (c = R, G, B), stored to three dense planes
+// (or, gray, the luma alone to one).  The per-channel form of the packed colour (terms_words):
+// per pixel pair and channel one packed add and one saturating pack, no byte shuffles.
+// ------------------------------------------------------------------------------------------
+// 4 pixels (two words of int16 pairs) of one channel -> 4 bytes
+template <bool LO>
+__device__ __forceinline__ uint32_t chan4(uint32_t y0, uint32_t y1, uint32_t t0, uint32_t t1) {
+    return pk_sat_add_hi<LO>(pk_sat_add<LO>(y0, t0), y1, t1);
+}
+template <bool LO>
+__device__ __forceinline__ void row_planar(const uint4& Yq, const uint32_t (&TR)[4], const uint32_t (&TG)[4],
+                                           const uint32_t (&TB)[4], uint32_t (&w)[6]) {
+    w[0] = chan4<LO>(Yq.x, Yq.y, TR[0], TR[1]);
+    w[1] = chan4<LO>(Yq.z, Yq.w, TR[2], TR[3]);
+    w[2] = chan4<LO>(Yq.x, Yq.y, TG[0], TG[1]);
+    w[3] = chan4<LO>(Yq.z, Yq.w, TG[2], TG[3]);
+    w[4] = chan4<LO>(Yq.x, Yq.y, TB[0], TB[1]);
+    w[5] = chan4<LO>(Yq.z, Yq.w, TB[2], TB[3]);
+}
+// fix_g_exact for the planar words: pixel j's G is byte j of the G words w[2], w[3]
+template <int SH>
+__device__ __forceinline__ void fix_g_planar(const uint4& Yq, const int16_t* s_pl, uint32_t cboff, uint32_t croff,
+                                             uint32_t exmask, uint32_t (&w)[6]) {
+    const uint32_t Y[4] = {Yq.x, Yq.y, Yq.z, Yq.w};
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const int u = j >> SH;
+        if ((exmask >> u) & 1u) {
+            const int y = (j & 1) ? int32_t(Y[j >> 1]) >> 16 : int(int16_t(Y[j >> 1] & 0xFFFFu));
+            const int g = color_g_exact(y, s_pl[cboff + u], s_pl[croff + u]);
+            w[2 + (j >> 2)] = (w[2 + (j >> 2)] & ~(0xFFu << (8 * (j & 3)))) | (uint32_t(g) << (8 * (j & 3)));
+        }
+    }
+}
+// 8 RGB pixels -> the planar words (the per-pixel branches)
+__device__ __forceinline__ void pack_planar(const uint32_t (&rgb)[8][3], uint32_t (&w)[6]) {
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int q = 0; q < 2; q++)
+            w[2 * c + q] = rgb[4 * q][c] | (rgb[4 * q + 1][c] << 8) | (rgb[4 * q + 2][c] << 16) | (rgb[4 * q + 3][c] << 24);
+}
+// Luma alone: clamp(Y + 128, 0, 255) of 8 samples (4 words of int16 pairs) -> 8 bytes
+__device__ __forceinline__ void row_gray(const uint4& Yq, uint32_t (&w)[2]) {
+    const uint32_t k128 = 0x00800080u;
+    w[0] = chan4<false>(Yq.x, Yq.y, k128, k128);
+    w[1] = chan4<false>(Yq.z, Yq.w, k128, k128);
+}
+// n <= 8 bytes of one plane row: one 8-byte store when aligned, two words when 4-aligned, else bytes
+// (store24's three cases)
+__device__ __forceinline__ void store8(uint8_t* dst, uint32_t w0, uint32_t w1, uint32_t n) {
+    const uintptr_t ad = reinterpret_cast<uintptr_t>(dst);
+    if (n == 8 && (ad & 3) == 0) {
+        if ((ad & 7) == 0) {
+            *gptr(reinterpret_cast<u32x2*>(dst)) = u32x2{w0, w1};
+        } else {
+            auto d1 = gptr(reinterpret_cast<uint32_t*>(dst));
+            d1[0] = w0;
+            d1[1] = w1;
+        }
+    } else {
+        auto d = gptr(dst);
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if (uint32_t(k) < n) d[k] = uint8_t((k < 4 ? w0 : w1) >> (8 * (k % 4)));
+    }
+}
+// n <= 4 bytes of one plane row (the 4-pixel halves)
+__device__ __forceinline__ void store4(uint8_t* dst, uint32_t w, uint32_t n) {
+    if (n == 4 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
+        *gptr(reinterpret_cast<uint32_t*>(dst)) = w;
+    } else {
+        auto d = gptr(dst);
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (uint32_t(k) < n) d[k] = uint8_t(w >> (8 * k));
+    }
+}
+// The planes of a planar image of HW = H * W pixels at pixel offset p = y * W + x: R, G, B planes
+// in that order, or (BGR) B, G, R
+template <bool BGR>
+__device__ __forceinline__ void store_planes8(uint8_t* out, size_t p, size_t HW, const uint32_t (&w)[6], uint32_t n) {
+    uint8_t* const d = out + p;
+    store8(d + (BGR ? 2 * HW : 0), w[0], w[1], n);
+    store8(d + HW, w[2], w[3], n);
+    store8(d + (BGR ? 0 : 2 * HW), w[4], w[5], n);
+}
+template <bool BGR>
+__device__ __forceinline__ void store_planes4(uint8_t* out, size_t p, size_t HW, const uint32_t (&w)[3], uint32_t n) {
+    uint8_t* const d = out + p;
+    store4(d + (BGR ? 2 * HW : 0), w[0], n);
+    store4(d + HW, w[1], n);
+    store4(d + (BGR ? 0 : 2 * HW), w[2], n);
+}
+// colour4x2 / colour4x1 for planar output: w[c] = the 4 bytes of channel c
+__device__ __forceinline__ void fix_g4_planar(const uint2& Yq, const int (&cb)[4], const int (&cr)[4], uint32_t exmask,
+                                              uint32_t (&w)[3]) {  // exmask bit j, cb[j], cr[j]: pixel j's sample
+    const uint32_t Y[2] = {Yq.x, Yq.y};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if ((exmask >> j) & 1u) {
+            const int y = (j & 1) ? int32_t(Y[j >> 1]) >> 16 : int(int16_t(Y[j >> 1] & 0xFFFFu));
+            const int g = color_g_exact(y, cb[j], cr[j]);
+            w[1] = (w[1] & ~(0xFFu << (8 * j))) | (uint32_t(g) << (8 * j));
+        }
+    }
+}
+__device__ __forceinline__ void colour4x2_planar(const int16_t* s_pl, uint32_t yoff, uint32_t ypitch, uint32_t cboff,
+                                                 uint32_t croff, uint32_t (&w0)[3], uint32_t (&w1)[3]) {
+    const uint32_t cbw = *reinterpret_cast<const uint32_t*>(s_pl + cboff);
+    const uint32_t crw = *reinterpret_cast<const uint32_t*>(s_pl + croff);
+    const int cb2[2] = {int(int16_t(cbw & 0xFFFFu)), int32_t(cbw) >> 16};
+    const int cr2[2] = {int(int16_t(crw & 0xFFFFu)), int32_t(crw) >> 16};
+    const ChromaTerms t0 = chroma_terms(cb2[0], cr2[0]), t1 = chroma_terms(cb2[1], cr2[1]);
+    const uint2 Y0 = *reinterpret_cast<const uint2*>(s_pl + yoff), Y1 = *reinterpret_cast<const uint2*>(s_pl + yoff + ypitch);
+    // word u = pixels 2u, 2u + 1 on sample u: the term in the low half
+    w0[0] = chan4<true>(Y0.x, Y0.y, uint32_t(t0.r), uint32_t(t1.r));
+    w0[1] = chan4<true>(Y0.x, Y0.y, uint32_t(t0.g), uint32_t(t1.g));
+    w0[2] = chan4<true>(Y0.x, Y0.y, uint32_t(t0.b), uint32_t(t1.b));
+    w1[0] = chan4<true>(Y1.x, Y1.y, uint32_t(t0.r), uint32_t(t1.r));
+    w1[1] = chan4<true>(Y1.x, Y1.y, uint32_t(t0.g), uint32_t(t1.g));
+    w1[2] = chan4<true>(Y1.x, Y1.y, uint32_t(t0.b), uint32_t(t1.b));
+    const uint32_t ex = (t0.exact ? 3u : 0u) | (t1.exact ? 12u : 0u);
+    if (__any(ex != 0u)) {
+        const int cb[4] = {cb2[0], cb2[0], cb2[1], cb2[1]}, cr[4] = {cr2[0], cr2[0], cr2[1], cr2[1]};
+        fix_g4_planar(Y0, cb, cr, ex, w0);
+        fix_g4_planar(Y1, cb, cr, ex, w1);
+    }
+}
+__device__ __forceinline__ void colour4x1_planar(const int16_t* s_pl, uint32_t yoff, uint32_t cboff, uint32_t croff,
+                                                 uint32_t (&w)[3]) {
+    const uint2 cbq = *reinterpret_cast<const uint2*>(s_pl + cboff);
+    const uint2 crq = *reinterpret_cast<const uint2*>(s_pl + croff);
+    const int cb[4] = {int(int16_t(cbq.x & 0xFFFFu)), int32_t(cbq.x) >> 16, int(int16_t(cbq.y & 0xFFFFu)), int32_t(cbq.y) >> 16};
+    const int cr[4] = {int(int16_t(crq.x & 0xFFFFu)), int32_t(crq.x) >> 16, int(int16_t(crq.y & 0xFFFFu)), int32_t(crq.y) >> 16};
+    ChromaTerms t[4];
+    uint32_t ex = 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        t[u] = chroma_terms(cb[u], cr[u]);
+        ex |= t[u].exact ? (1u << u) : 0u;
+    }
+    const uint2 Y0 = *reinterpret_cast<const uint2*>(s_pl + yoff);
+    w[0] = chan4<false>(Y0.x, Y0.y, r_pair(cr[0], cr[1]), r_pair(cr[2], cr[3]));
+    w[1] = chan4<false>(Y0.x, Y0.y, pair16(t[0].g, t[1].g), pair16(t[2].g, t[3].g));
+    w[2] = chan4<false>(Y0.x, Y0.y, b_pair(cb[0], cb[1]), b_pair(cb[2], cb[3]));
+    if (__any(ex != 0u)) fix_g4_planar(Y0, cb, cr, ex, w);
 }
 
 // One wave per tile of tile_mcus x tile_mrows MCUs (host-chosen, <= 64 blocks):
@@ -3673,7 +3832,8 @@ __device__ __forceinline__ void zero_staging(uint32_t* s_buf, uint32_t lane) {
 //  * EXACT = false (k_idct_color): a wave with a coefficient beyond the fast IDCT's range (never
 //    seen in real images) appends its tile to slow_tiles and returns false;
 //  * EXACT = true (k_idct_color_exact) decodes those tiles with the exact IDCT form.
-template <bool EXACT, int M, class Mid>
+//  * F (kFmt*): the output format, a compile-time parameter of the colour/store stage only.
+template <bool EXACT, int M, uint32_t F, class Mid>
 __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDesc& im, uint32_t img, uint32_t tile,
                                                  const TileGeo& G, const TileLaneGeo& L, int dc_pred, bool esc,
                                                  uint32_t* s_buf, const int* s_qz, Mid&& mid) {
@@ -3821,7 +3981,9 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
     // (luma below the maximum factor, e.g. Y 1x1 with 2x1 chroma: the generic instance only)
     const uint32_t shx0 = TM_::shx(im, 0), shy0 = TM_::shy(im, 0);
     const uint32_t cmode = nc == 1 ? 3u : ((shx1 == shx2 && (shx0 | shy0) == 0u) ? shx1 : 4u);
-    const bool pair = cmode <= 2u && shy1 >= 1u && shy2 >= 1u;  // wave-uniform; th is even then
+    constexpr bool kGray = F == kFmtGray, kPlanar = (F & kFmtPlanar) != 0, kBgr = (F & kFmtBgr) != 0;
+    // (gray: single rows of luma, no chroma to share)
+    const bool pair = !kGray && cmode <= 2u && shy1 >= 1u && shy2 >= 1u;  // wave-uniform; th is even then
     const uint32_t rows = pair ? 2u : 1u, ngy = th / rows;
     uint8_t* out = reinterpret_cast<uint8_t*>(im.rgb);
     // lane -> (row group gy, column group gc), advanced by 64 groups per iteration
@@ -3831,8 +3993,9 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
     // half full, it is done as 4-pixel halves of the remaining groups (colour4x2) instead
     const uint32_t ngroups = gpr * ngy, nfull = ngroups / kIdctThreads, nrem = ngroups - nfull * kIdctThreads;
     // 4:4:4 (per-pixel chroma, single rows) likewise, as 4-pixel halves of one row (colour4x1)
-    const bool halves = nrem != 0u && 2u * nrem <= kIdctThreads &&
+    const bool halves = !kGray && nrem != 0u && 2u * nrem <= kIdctThreads &&
                         ((pair && cmode == 1u) || (!pair && cmode == 0u));  // wave-uniform
+    const size_t HW = size_t(H) * W;  // (planar: pixels per plane)
     const uint32_t nsteps = halves ? nfull : ~0u;
     for (uint32_t st = 0; gy < ngy && st < nsteps;
          st++, gy += step_y + (gc + step_c >= gpr ? 1u : 0u), gc = gc + step_c >= gpr ? gc + step_c - gpr : gc + step_c) {
@@ -3842,16 +4005,84 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
         const uint32_t yoff = pbase[0] + (py >> shy0) * ppitch[0] + (gx >> shx0);
         const uint32_t cboff = pbase[1] + (py >> shy1) * ppitch[1] + (gx >> shx1);
         const uint32_t croff = pbase[2] + (py >> shy2) * ppitch[2] + (gx >> shx2);
+        if constexpr (kGray) {  // luma alone, replicated when it is below the maximum factor
+            uint4 Yq;
+            if (shx0 == 0u) {  // wave-uniform
+                Yq = *reinterpret_cast<const uint4*>(s_pl + yoff);
+            } else {
+                int Y0[8];
+                load8_samples(s_pl, yoff, shx0, Y0);
+                Yq = make_uint4(pair16(Y0[0], Y0[1]), pair16(Y0[2], Y0[3]), pair16(Y0[4], Y0[5]), pair16(Y0[6], Y0[7]));
+            }
+            uint32_t g[2];
+            row_gray(Yq, g);
+            store8(out + size_t(y) * W + x, g[0], g[1], min(8u, W - x));
+            continue;
+        }
         uint32_t w0[6], w1[6];
+        if constexpr (kPlanar) {
+            if (cmode <= 2u) {  // the packed colour in its per-channel form (terms_words)
+                uint32_t TR[4], TG[4], TB[4], ex;
+                switch (cmode) {
+                    case 0: ex = terms_words<0>(s_pl, cboff, croff, TR, TG, TB); break;
+                    case 1: ex = terms_words<1>(s_pl, cboff, croff, TR, TG, TB); break;
+                    default: ex = terms_words<2>(s_pl, cboff, croff, TR, TG, TB); break;
+                }
+                const uint4 Y0q = *reinterpret_cast<const uint4*>(s_pl + yoff);
+                if (cmode == 0u) row_planar<false>(Y0q, TR, TG, TB, w0);
+                else row_planar<true>(Y0q, TR, TG, TB, w0);
+                uint4 Y1q = make_uint4(0, 0, 0, 0);
+                if (pair) {
+                    Y1q = *reinterpret_cast<const uint4*>(s_pl + yoff + ppitch[0]);
+                    if (cmode == 0u) row_planar<false>(Y1q, TR, TG, TB, w1);
+                    else row_planar<true>(Y1q, TR, TG, TB, w1);
+                }
+                if (__any(ex != 0u)) {  // uniform over the lanes in this step
+                    switch (cmode) {
+                        case 0: fix_g_planar<0>(Y0q, s_pl, cboff, croff, ex, w0); break;
+                        case 1: fix_g_planar<1>(Y0q, s_pl, cboff, croff, ex, w0); break;
+                        default: fix_g_planar<2>(Y0q, s_pl, cboff, croff, ex, w0); break;
+                    }
+                    if (pair) {
+                        switch (cmode) {
+                            case 0: fix_g_planar<0>(Y1q, s_pl, cboff, croff, ex, w1); break;
+                            case 1: fix_g_planar<1>(Y1q, s_pl, cboff, croff, ex, w1); break;
+                            default: fix_g_planar<2>(Y1q, s_pl, cboff, croff, ex, w1); break;
+                        }
+                    }
+                }
+            } else {  // per pixel, as below (a helper shared with that branch changed the default generic
+                      // instance's code, so the few lines are repeated)
+                int Y0[8];
+                uint32_t rgb[8][3];
+                if (cmode == 3u) {
+                    load_plane<0>(s_pl, yoff, Y0);
+                    colour8<3>(Y0, s_pl, cboff, croff, rgb);
+                } else {
+                    int Cb[8], Cr[8];
+                    load8_samples(s_pl, yoff, shx0, Y0);
+                    load8_samples(s_pl, cboff, shx1, Cb);
+                    load8_samples(s_pl, croff, shx2, Cr);
+#pragma unroll
+                    for (int j = 0; j < 8; j++)
+                        colour_px(Y0[j], Cb[j], Cr[j], chroma_terms(Cb[j], Cr[j]), rgb[j][0], rgb[j][1], rgb[j][2]);
+                }
+                pack_planar(rgb, w0);
+            }
+            const size_t p = size_t(y) * W + x;
+            store_planes8<kBgr>(out, p, HW, w0, min(8u, W - x));
+            if (pair && y + 1 < H) store_planes8<kBgr>(out, p + W, HW, w1, min(8u, W - x));
+            continue;
+        }
         if (cmode <= 2u) {  // wave-uniform: both chroma planes share one horizontal factor
             // packed integer colour for every pixel; G of the few pixels whose chroma sample needs
             // the reference's double-precision path is patched afterwards (about 5 % of the
             // lane-steps have one such sample in some lane)
             uint32_t TA[4], TB[4], TC[4], ex;
             switch (cmode) {
-                case 0: ex = terms_il<0>(s_pl, cboff, croff, TA, TB, TC); break;
-                case 1: ex = terms_il<1>(s_pl, cboff, croff, TA, TB, TC); break;
-                default: ex = terms_il<2>(s_pl, cboff, croff, TA, TB, TC); break;
+                case 0: ex = terms_il<0, kBgr>(s_pl, cboff, croff, TA, TB, TC); break;
+                case 1: ex = terms_il<1, kBgr>(s_pl, cboff, croff, TA, TB, TC); break;
+                default: ex = terms_il<2, kBgr>(s_pl, cboff, croff, TA, TB, TC); break;
             }
             const uint4 Y0q = *reinterpret_cast<const uint4*>(s_pl + yoff);
             row_rgb_il(Y0q, TA, TB, TC, w0);
@@ -3887,7 +4118,7 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
                 load8_samples(s_pl, croff, shx2, Cr);
 #pragma unroll
                 for (int j = 0; j < 8; j++)
-                    colour_px(Y0[j], Cb[j], Cr[j], chroma_terms(Cb[j], Cr[j]), rgb[j][0], rgb[j][1], rgb[j][2]);
+                    colour_px(Y0[j], Cb[j], Cr[j], chroma_terms(Cb[j], Cr[j]), rgb[j][kBgr ? 2 : 0], rgb[j][1], rgb[j][kBgr ? 0 : 2]);
             }
             pack24(rgb, w0);
         }
@@ -3904,8 +4135,13 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
         const uint32_t y = y_tile + py, x = x_tile + gx;
         if (y < H && x < W) {
             uint32_t w0[3];
-            colour4x1(s_pl, pbase[0] + py * ppitch[0] + gx, pbase[1] + py * ppitch[1] + gx, pbase[2] + py * ppitch[2] + gx, w0);
-            store12(rgb_at(out, y, W3, x), w0, min(4u, W - x));
+            if constexpr (kPlanar) {
+                colour4x1_planar(s_pl, pbase[0] + py * ppitch[0] + gx, pbase[1] + py * ppitch[1] + gx, pbase[2] + py * ppitch[2] + gx, w0);
+                store_planes4<kBgr>(out, size_t(y) * W + x, HW, w0, min(4u, W - x));
+            } else {
+                colour4x1<kBgr>(s_pl, pbase[0] + py * ppitch[0] + gx, pbase[1] + py * ppitch[1] + gx, pbase[2] + py * ppitch[2] + gx, w0);
+                store12(rgb_at(out, y, W3, x), w0, min(4u, W - x));
+            }
         }
     } else if (halves && lane < 2u * nrem) {
         const uint32_t g = nfull * kIdctThreads + (lane >> 1);
@@ -3914,11 +4150,19 @@ __device__ __forceinline__ bool idct_colour_tile(const BatchDev& b, const ImgDes
         const uint32_t y = y_tile + py, x = x_tile + gx;
         if (y < H && x < W) {
             uint32_t w0[3], w1[3];
-            colour4x2(s_pl, pbase[0] + py * ppitch[0] + gx, ppitch[0], pbase[1] + (py >> 1) * ppitch[1] + (gx >> 1),
-                      pbase[2] + (py >> 1) * ppitch[2] + (gx >> 1), w0, w1);
-            uint8_t* const p0 = rgb_at(out, y, W3, x);
-            store12(p0, w0, min(4u, W - x));
-            if (y + 1 < H) store12(p0 + W3, w1, min(4u, W - x));
+            if constexpr (kPlanar) {
+                colour4x2_planar(s_pl, pbase[0] + py * ppitch[0] + gx, ppitch[0], pbase[1] + (py >> 1) * ppitch[1] + (gx >> 1),
+                                 pbase[2] + (py >> 1) * ppitch[2] + (gx >> 1), w0, w1);
+                const size_t p = size_t(y) * W + x;
+                store_planes4<kBgr>(out, p, HW, w0, min(4u, W - x));
+                if (y + 1 < H) store_planes4<kBgr>(out, p + W, HW, w1, min(4u, W - x));
+            } else {
+                colour4x2<kBgr>(s_pl, pbase[0] + py * ppitch[0] + gx, ppitch[0], pbase[1] + (py >> 1) * ppitch[1] + (gx >> 1),
+                                pbase[2] + (py >> 1) * ppitch[2] + (gx >> 1), w0, w1);
+                uint8_t* const p0 = rgb_at(out, y, W3, x);
+                store12(p0, w0, min(4u, W - x));
+                if (y + 1 < H) store12(p0 + W3, w1, min(4u, W - x));
+            }
         }
     }
     return true;
@@ -3952,7 +4196,7 @@ __device__ __forceinline__ DcPred load_dcpred(const BatchDev& b, const ImgDesc& 
 #ifndef JD_IDCT_PRIO_LATE
 #define JD_IDCT_PRIO_LATE 0  // (experiment builds) the reverse: priority raised once the loads are out
 #endif
-template <int M>
+template <int M, uint32_t F = kFmtRgb>
 __global__ __launch_bounds__(kIdctThreads, JD_IDCT_LB) void k_idct_color(BatchDev b) {
     __shared__ __attribute__((aligned(16))) uint32_t s_buf[kIdctBufWords];
     __shared__ __attribute__((aligned(16))) int s_qz[kQzWords];
@@ -3979,11 +4223,12 @@ __global__ __launch_bounds__(kIdctThreads, JD_IDCT_LB) void k_idct_color(BatchDe
     __syncthreads();
     if (JD_ABL_PHASE == 2) return;  // diagnostic builds: no IDCT and colour (the staging rows are kept)
     JD_STAMP_AT(2);
-    idct_colour_tile<false, M>(b, im, img, tile, G, L, dc_pred, R.esc, s_buf, s_qz, [&] { JD_STAMP_AT(3); });
+    idct_colour_tile<false, M, F>(b, im, img, tile, G, L, dc_pred, R.esc, s_buf, s_qz, [&] { JD_STAMP_AT(3); });
     JD_STAMP_AT(4);
 }
 
 // The tiles k_idct_color left (grid-stride over the list; empty in practice).
+template <uint32_t F = kFmtRgb>
 __global__ __launch_bounds__(kIdctThreads) void k_idct_color_exact(BatchDev b) {
     __shared__ __attribute__((aligned(16))) uint32_t s_buf[kIdctBufWords];
     __shared__ __attribute__((aligned(16))) int s_qz[kQzWords];
@@ -4006,7 +4251,7 @@ __global__ __launch_bounds__(kIdctThreads) void k_idct_color_exact(BatchDev b) {
         load_entry_quads(R, E);
         scatter_entries(s_buf, staging_base(lane), R, E);
         __syncthreads();
-        idct_colour_tile<true, kModeGen>(b, im, tr.img, tr.tile, G, L, dc_pred, R.esc, s_buf, s_qz, [] {});
+        idct_colour_tile<true, kModeGen, F>(b, im, tr.img, tr.tile, G, L, dc_pred, R.esc, s_buf, s_qz, [] {});
     }
 }
 
@@ -4124,7 +4369,8 @@ __device__ __forceinline__ void fancy_row8(const FancyWin& P, uint32_t gx, uint3
 
 // 8 pixels: Y (1x1 window), filtered chroma, then the packed integer colour of k_idct_color (terms
 // per pixel here) with the same double-precision G patch.
-template <int MODE>
+// F (kFmt*): w is the 24 interleaved bytes (R, G, B or B, G, R), or the planar words (row_planar).
+template <int MODE, uint32_t F = kFmtRgb>
 __device__ __forceinline__ void fancy_colour8(const FancyWin (&P)[3], uint32_t gx, uint32_t y, uint32_t (&w)[6]) {
     const uint4 Yq = *reinterpret_cast<const uint4*>(P[0].row(int(y)) + (int(gx) - P[0].c0));
     int cb[8], cr[8];
@@ -4140,7 +4386,9 @@ __device__ __forceinline__ void fancy_colour8(const FancyWin (&P)[3], uint32_t g
         TG[u] = pair16(t0.g, t1.g);
         TB[u] = pair16(t0.b, t1.b);
     }
-    row_rgb_packed<false>(Yq, TR, TG, TB, w);
+    if constexpr ((F & kFmtPlanar) != 0) row_planar<false>(Yq, TR, TG, TB, w);
+    else if constexpr ((F & kFmtBgr) != 0) row_rgb_packed<false>(Yq, TB, TG, TR, w);
+    else row_rgb_packed<false>(Yq, TR, TG, TB, w);
     if (__any(ex != 0u)) {
         const uint32_t Y[4] = {Yq.x, Yq.y, Yq.z, Yq.w};
 #pragma unroll
@@ -4148,7 +4396,7 @@ __device__ __forceinline__ void fancy_colour8(const FancyWin (&P)[3], uint32_t g
             if ((ex >> j) & 1u) {
                 const int yv = (j & 1) ? int32_t(Y[j >> 1]) >> 16 : int(int16_t(Y[j >> 1] & 0xFFFFu));
                 const int g = color_g_exact(yv, cb[j], cr[j]);
-                const int byte = 3 * j + 1;
+                const int byte = (F & kFmtPlanar) ? 8 + j : 3 * j + 1;  // planar: byte j of the G words w[2], w[3]
                 w[byte >> 2] = (w[byte >> 2] & ~(0xFFu << (8 * (byte & 3)))) | (uint32_t(g) << (8 * (byte & 3)));
             }
         }
@@ -4168,7 +4416,7 @@ static_assert((kFancyRows * (kFancyCols / 8) + kFancyThreads - 1) / kFancyThread
 // h2v2 filter, 4:2:2 h2v1, 4:4:4 none (all vectorised, fancy_colour8, with the layout's ratios as
 // compile-time constants); every other layout (h1v2, grayscale, other ratios) takes the per-pixel
 // fancy_win path with ratios from the image descriptor.
-template <int M>
+template <int M, uint32_t F = kFmtRgb>
 __global__ __launch_bounds__(kFancyThreads, JD_FANCY_LB) void k_colour_fancy(BatchDev b) {
     __shared__ __attribute__((aligned(16))) int16_t s_win[3][kFancyRows * kFancyCols];
     constexpr bool kFixed = M != kModeGen;
@@ -4187,31 +4435,31 @@ __global__ __launch_bounds__(kFancyThreads, JD_FANCY_LB) void k_colour_fancy(Bat
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const uint32_t cc = uint32_t(c) < nc ? uint32_t(c) : 0u;
-            FancyWin& F = P[c];
+            FancyWin& Fw = P[c];
             if (kFixed) {  // Y 1x1, chroma 2^kLgRx x 2^kLgRy
                 const uint32_t lx = c ? kLgRx : 0u, ly = c ? kLgRy : 0u;
-                F.rx = 1u << lx;
-                F.ry = 1u << ly;
-                F.cw = (W + F.rx - 1) >> lx;
-                F.ch = (H + F.ry - 1) >> ly;
+                Fw.rx = 1u << lx;
+                Fw.ry = 1u << ly;
+                Fw.cw = (W + Fw.rx - 1) >> lx;
+                Fw.ch = (H + Fw.ry - 1) >> ly;
                 pitch[c] = im.mcux * ((c ? 1u : 1u << kLgRx) * 8);
                 prow[c] = im.mcuy * ((c ? 1u : 1u << kLgRy) * 8);
             } else {
-                F.rx = im.hmax / im.h[cc];
-                F.ry = im.vmax / im.v[cc];
-                F.cw = (W * im.h[cc] + im.hmax - 1) / im.hmax;
-                F.ch = (H * im.v[cc] + im.vmax - 1) / im.vmax;
+                Fw.rx = im.hmax / im.h[cc];
+                Fw.ry = im.vmax / im.v[cc];
+                Fw.cw = (W * im.h[cc] + im.hmax - 1) / im.hmax;
+                Fw.ch = (H * im.v[cc] + im.vmax - 1) / im.vmax;
                 pitch[c] = im.mcux * im.h[cc] * 8;
                 prow[c] = im.mcuy * im.v[cc] * 8;
             }
-            const uint32_t xs = kFixed ? (x0 >> (c ? kLgRx : 0u)) : x0 / F.rx;
-            const uint32_t xe = kFixed ? ((x0 + kFancyW - 1) >> (c ? kLgRx : 0u)) : (x0 + kFancyW - 1) / F.rx;
+            const uint32_t xs = kFixed ? (x0 >> (c ? kLgRx : 0u)) : x0 / Fw.rx;
+            const uint32_t xe = kFixed ? ((x0 + kFancyW - 1) >> (c ? kLgRx : 0u)) : (x0 + kFancyW - 1) / Fw.rx;
             const int c0 = max(0, (int(xs) - 1) & ~7);
             const int c1 = min(int(pitch[c]), int((xe + 9) & ~7u));
-            F.s = s_win[c];
-            F.c0 = c0;
-            F.ncols = c1 - c0;
-            qpr[c] = uint32_t(F.ncols) >> 3;
+            Fw.s = s_win[c];
+            Fw.c0 = c0;
+            Fw.ncols = c1 - c0;
+            qpr[c] = uint32_t(Fw.ncols) >> 3;
             qmagic[c] = (65536u + qpr[c] - 1u) / qpr[c];
             src[c] = reinterpret_cast<const int16_t*>(im.planes) + off + c0;
             if (uint32_t(c) < nc) off += size_t(pitch[c]) * prow[c];
@@ -4268,8 +4516,9 @@ __global__ __launch_bounds__(kFancyThreads, JD_FANCY_LB) void k_colour_fancy(Bat
         const uint32_t y = y0 + (t >> 4), gx = x0 + ((t & 15u) << 3);
         if (y < H && gx < W) {
             uint32_t w[6];
+            constexpr bool kPlanar = (F & kFmtPlanar) != 0, kBgr = (F & kFmtBgr) != 0;
             if (kFixed) {
-                fancy_colour8<kFilt>(P, gx, y, w);
+                fancy_colour8<kFilt, F>(P, gx, y, w);
             } else {  // grayscale, h1v2, a subsampled Y, or chroma planes with different ratios: per pixel
                 uint32_t rgb[8][3];
 #pragma unroll
@@ -4280,12 +4529,17 @@ __global__ __launch_bounds__(kFancyThreads, JD_FANCY_LB) void k_colour_fancy(Bat
                         rgb[j][0] = rgb[j][1] = rgb[j][2] = clamp_u8(yv + 128);
                     } else {
                         const int cb = fancy_win(P[1], x, y), cr = fancy_win(P[2], x, y);
-                        colour_px(yv, cb, cr, chroma_terms(cb, cr), rgb[j][0], rgb[j][1], rgb[j][2]);
+                        colour_px(yv, cb, cr, chroma_terms(cb, cr), rgb[j][(kBgr && !kPlanar) ? 2 : 0], rgb[j][1],
+                                  rgb[j][(kBgr && !kPlanar) ? 0 : 2]);
                     }
                 }
-                pack24(rgb, w);
+                if constexpr (kPlanar) pack_planar(rgb, w);
+                else pack24(rgb, w);
             }
-            store24(rgb_at(reinterpret_cast<uint8_t*>(im.rgb), y, 3u * W, gx), w, min(8u, W - gx));
+            if constexpr (kPlanar)
+                store_planes8<kBgr>(reinterpret_cast<uint8_t*>(im.rgb), size_t(y) * W + gx, size_t(H) * W, w, min(8u, W - gx));
+            else
+                store24(rgb_at(reinterpret_cast<uint8_t*>(im.rgb), y, 3u * W, gx), w, min(8u, W - gx));
         }
         if (!next) break;
         __syncthreads();  // every read of this band's windows is done
@@ -4416,6 +4670,31 @@ static hipError_t allow_lds_big(size_t lds) {
     return e;
 }
 
+template <uint32_t F>
+static void launch_idct(const BatchDev& b, hipStream_t s) {
+    if (b.mode_cnt[kModeGen])
+        hipLaunchKernelGGL((k_idct_color<kModeGen, F>), dim3(b.mode_max_tiles[kModeGen], b.mode_cnt[kModeGen]), dim3(kIdctThreads), 0, s, b);
+    if (b.mode_cnt[kMode420])
+        hipLaunchKernelGGL((k_idct_color<kMode420, F>), dim3(b.mode_max_tiles[kMode420], b.mode_cnt[kMode420]), dim3(kIdctThreads), 0, s, b);
+    if (b.mode_cnt[kMode422])
+        hipLaunchKernelGGL((k_idct_color<kMode422, F>), dim3(b.mode_max_tiles[kMode422], b.mode_cnt[kMode422]), dim3(kIdctThreads), 0, s, b);
+    if (b.mode_cnt[kMode444])
+        hipLaunchKernelGGL((k_idct_color<kMode444, F>), dim3(b.mode_max_tiles[kMode444], b.mode_cnt[kMode444]), dim3(kIdctThreads), 0, s, b);
+    hipLaunchKernelGGL(k_idct_color_exact<F>, dim3(1024), dim3(kIdctThreads), 0, s, b);
+}
+template <uint32_t F>
+static void launch_fancy(const BatchDev& b, hipStream_t s) {
+    const dim3 g(b.max_fancy_wgs & 0xFFFFu, b.max_fancy_wgs >> 16, 1);
+    if (b.mode_cnt[kModeGen])
+        hipLaunchKernelGGL((k_colour_fancy<kModeGen, F>), dim3(g.x, g.y, b.mode_cnt[kModeGen]), dim3(kFancyThreads), 0, s, b);
+    if (b.mode_cnt[kMode420])
+        hipLaunchKernelGGL((k_colour_fancy<kMode420, F>), dim3(g.x, g.y, b.mode_cnt[kMode420]), dim3(kFancyThreads), 0, s, b);
+    if (b.mode_cnt[kMode422])
+        hipLaunchKernelGGL((k_colour_fancy<kMode422, F>), dim3(g.x, g.y, b.mode_cnt[kMode422]), dim3(kFancyThreads), 0, s, b);
+    if (b.mode_cnt[kMode444])
+        hipLaunchKernelGGL((k_colour_fancy<kMode444, F>), dim3(g.x, g.y, b.mode_cnt[kMode444]), dim3(kFancyThreads), 0, s, b);
+}
+
 hipError_t launch_kernel(int k, const BatchDev& b, hipStream_t s) {
     if (!b.nimg) return hipSuccess;
     const size_t lds = piece_lds_bytes(b.max_slots, kPieceThreads);
@@ -4479,28 +4758,26 @@ hipError_t launch_kernel(int k, const BatchDev& b, hipStream_t s) {
             break;
         case 9:
             if (!b.max_tiles) break;
-            // one launch per sampling layout present in the batch (k_idct_color<M> is specialised)
-            if (b.mode_cnt[kModeGen])
-                hipLaunchKernelGGL(k_idct_color<kModeGen>, dim3(b.mode_max_tiles[kModeGen], b.mode_cnt[kModeGen]), dim3(kIdctThreads), 0, s, b);
-            if (b.mode_cnt[kMode420])
-                hipLaunchKernelGGL(k_idct_color<kMode420>, dim3(b.mode_max_tiles[kMode420], b.mode_cnt[kMode420]), dim3(kIdctThreads), 0, s, b);
-            if (b.mode_cnt[kMode422])
-                hipLaunchKernelGGL(k_idct_color<kMode422>, dim3(b.mode_max_tiles[kMode422], b.mode_cnt[kMode422]), dim3(kIdctThreads), 0, s, b);
-            if (b.mode_cnt[kMode444])
-                hipLaunchKernelGGL(k_idct_color<kMode444>, dim3(b.mode_max_tiles[kMode444], b.mode_cnt[kMode444]), dim3(kIdctThreads), 0, s, b);
-            hipLaunchKernelGGL(k_idct_color_exact, dim3(1024), dim3(kIdctThreads), 0, s, b);
+            // one launch per sampling layout present in the batch (k_idct_color<M, F> is specialised
+            // by layout and by the batch's output format)
+            switch (b.out_fmt) {
+                case kFmtRgb: launch_idct<kFmtRgb>(b, s); break;
+                case kFmtBgr: launch_idct<kFmtBgr>(b, s); break;
+                case kFmtPlanar: launch_idct<kFmtPlanar>(b, s); break;
+                case kFmtPlanar | kFmtBgr: launch_idct<kFmtPlanar | kFmtBgr>(b, s); break;
+                case kFmtGray: launch_idct<kFmtGray>(b, s); break;
+                default: return hipErrorInvalidValue;
+            }
             break;
         case 10:
             if (b.fancy && b.max_fancy_wgs) {  // one launch per sampling layout present in the batch
-                const dim3 g(b.max_fancy_wgs & 0xFFFFu, b.max_fancy_wgs >> 16, 1);
-                if (b.mode_cnt[kModeGen])
-                    hipLaunchKernelGGL(k_colour_fancy<kModeGen>, dim3(g.x, g.y, b.mode_cnt[kModeGen]), dim3(kFancyThreads), 0, s, b);
-                if (b.mode_cnt[kMode420])
-                    hipLaunchKernelGGL(k_colour_fancy<kMode420>, dim3(g.x, g.y, b.mode_cnt[kMode420]), dim3(kFancyThreads), 0, s, b);
-                if (b.mode_cnt[kMode422])
-                    hipLaunchKernelGGL(k_colour_fancy<kMode422>, dim3(g.x, g.y, b.mode_cnt[kMode422]), dim3(kFancyThreads), 0, s, b);
-                if (b.mode_cnt[kMode444])
-                    hipLaunchKernelGGL(k_colour_fancy<kMode444>, dim3(g.x, g.y, b.mode_cnt[kMode444]), dim3(kFancyThreads), 0, s, b);
+                switch (b.out_fmt) {  // (gray never runs the fancy path: jd_runtime.cpp)
+                    case kFmtRgb: launch_fancy<kFmtRgb>(b, s); break;
+                    case kFmtBgr: launch_fancy<kFmtBgr>(b, s); break;
+                    case kFmtPlanar: launch_fancy<kFmtPlanar>(b, s); break;
+                    case kFmtPlanar | kFmtBgr: launch_fancy<kFmtPlanar | kFmtBgr>(b, s); break;
+                    default: return hipErrorInvalidValue;
+                }
             }
             break;
         default: return hipErrorInvalidValue;

@@ -45,6 +45,21 @@ struct DevBuf {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Output format of a context (jd.h JD_FLAG_OUT_*): every size of an image's output goes through
+// out_bytes_of, the kernels take out_format (jd_internal.hpp kFmt*).
+constexpr unsigned kOutFlags = JD_FLAG_OUT_PLANAR | JD_FLAG_OUT_BGR | JD_FLAG_OUT_GRAY;
+inline bool out_flags_valid(unsigned flags) {
+    return !(flags & JD_FLAG_OUT_GRAY) || !(flags & (JD_FLAG_OUT_PLANAR | JD_FLAG_OUT_BGR));
+}
+inline uint32_t out_channels(unsigned flags) { return (flags & JD_FLAG_OUT_GRAY) ? 1u : 3u; }
+inline size_t out_bytes_of(const jd_header& h, unsigned flags) {
+    return size_t(h.width) * size_t(h.height) * out_channels(flags);
+}
+inline uint32_t out_format(unsigned flags) {
+    if (flags & JD_FLAG_OUT_GRAY) return kFmtGray;
+    return ((flags & JD_FLAG_OUT_PLANAR) ? kFmtPlanar : kFmtRgb) | ((flags & JD_FLAG_OUT_BGR) ? kFmtBgr : 0u);
+}
+
 // Host-input staging copy into pinned memory with streaming (non-temporal) stores: the staging
 // buffer is only read again by the H2D DMA, so its lines need not be fetched (no read-for-
 // ownership) nor kept in the caches.  dst is 16-byte aligned (staging offsets are 256-B aligned,
@@ -187,6 +202,7 @@ struct Pending {
     hipEvent_t done = nullptr;
     hipEvent_t ev[JD_NUM_KERNELS][2] = {};
     bool timing = false, fancy = false;
+    double out_px_bytes = 3;                    // output bytes per pixel (1: gray)
     double blocks = 0, pixels = 0, ecs = 0, nsub = 0, nseg = 0, chunks = 0, tiles = 0, piece_bits = 0, piece_overlap = 0;
     double t_plan = 0, t_upload = 0;
     // what a retry needs (run_retries): the items, their parsed headers and device bytes (dev_addr:
@@ -743,7 +759,7 @@ jd_status launch_batch(jd_ctx* ctx, const jd_item* items, int lo, int hi, jd_res
     for (int i = lo; i < hi; i++) {
         if (ctx->pst[i] != JD_OK) continue;
         if (!items[i].jpeg_dev && !registered[size_t(i)]) in_bytes += align_up(items[i].len + 64, 256);
-        if (!rgb_on_device) out_bytes += align_up(size_t(ctx->parsed[i].hdr.width) * ctx->parsed[i].hdr.height * 3, 256);
+        if (!rgb_on_device) out_bytes += align_up(out_bytes_of(ctx->parsed[i].hdr, ctx->flags), 256);
     }
     for (Span& sp : spans) {  // after the staged inputs in the slot's device input pool
         sp.off = in_bytes + reg_bytes;
@@ -825,7 +841,7 @@ jd_status launch_batch(jd_ctx* ctx, const jd_item* items, int lo, int hi, jd_res
                 out_addr[i] = reinterpret_cast<uint64_t>(items[i].rgb);
             } else {
                 out_addr[i] = reinterpret_cast<uint64_t>(ctx->output.p) + off;
-                off += align_up(size_t(ctx->parsed[i].hdr.width) * ctx->parsed[i].hdr.height * 3, 256);
+                off += align_up(out_bytes_of(ctx->parsed[i].hdr, ctx->flags), 256);
             }
         }
     }
@@ -848,7 +864,8 @@ jd_status launch_batch(jd_ctx* ctx, const jd_item* items, int lo, int hi, jd_res
     if (nimg) {
         HIPCHK(ctx, ensure_dev(ctx, sl.d_comp, std::max<size_t>(16, P.comp_bytes)));
         for (ImgDesc& d : P.imgs) d.comp += reinterpret_cast<uint64_t>(sl.d_comp.p);
-        const bool fancy = (ctx->flags & JD_FLAG_FANCY_UPSAMPLING) != 0;
+        // (gray output never runs the fancy path: no plane pool, no k_colour_fancy)
+        const bool fancy = (ctx->flags & JD_FLAG_FANCY_UPSAMPLING) != 0 && !(ctx->flags & JD_FLAG_OUT_GRAY);
         uint32_t max_fancy_wgs = 0;
         if (fancy) {  // int16 component planes over the padded MCU grid, 256-B aligned per image
             std::vector<size_t> poff(P.imgs.size());
@@ -1006,6 +1023,7 @@ jd_status launch_batch(jd_ctx* ctx, const jd_item* items, int lo, int hi, jd_res
             b.stamps = static_cast<unsigned long long*>(sl.d_stamps.p);
         }
         b.fancy = fancy ? 1u : 0u;
+        b.out_fmt = out_format(ctx->flags);
         b.max_fancy_wgs = max_fancy_wgs;
         if (const char* e = std::getenv("JD_FIX_ROUND_CAP")) b.fix_round_cap = uint32_t(std::strtoul(e, nullptr, 0));
         b.skip_redo = std::getenv("JD_SKIP_REDO") ? 1u : 0u;
@@ -1055,6 +1073,7 @@ jd_status launch_batch(jd_ctx* ctx, const jd_item* items, int lo, int hi, jd_res
         HIPCHK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(pd.host) + kCtrBytes, b.status, nimg * 4, hipMemcpyDeviceToHost, s));
         pd.timing = timing;
         pd.fancy = fancy;
+        pd.out_px_bytes = double(out_channels(ctx->flags));
         pd.blocks = double(P.total_blocks);
         pd.pixels = P.pixels;
         pd.ecs = P.ecs_bytes;
@@ -1082,7 +1101,7 @@ jd_status launch_batch(jd_ctx* ctx, const jd_item* items, int lo, int hi, jd_res
         pd.h[i - lo] = ctx->parsed[i].hdr.height;
         if (!rgb_on_device && out_addr[i] && items[i].rgb && ctx->pst[i] == JD_OK)
             pd.host_copies.push_back({reinterpret_cast<uint64_t>(items[i].rgb), out_addr[i],
-                                      uint64_t(ctx->parsed[i].hdr.width) * ctx->parsed[i].hdr.height * 3});
+                                      uint64_t(out_bytes_of(ctx->parsed[i].hdr, ctx->flags))});
     }
     pd.worst = worst;
     pd.rgb_on_device = rgb_on_device;
@@ -1152,9 +1171,9 @@ jd_status finish_batch(jd_ctx* ctx, Pending& pd) {
             nsubd * 20,                                        // k_chain: counts in, first MCU / count out
             blocks * 12 + nsubd * 24,                          // k_gather: records in, BlockInfo out
             blocks * 8 + pd.tiles * 48,                        // k_dc_pred: BlockInfo read, tile sums, scan
-            blocks * 8 + entries * 2 + (fancy ? blocks * 128 : pd.pixels * 3),  // k_idct_color: coefficients
-                                                                                 // in, RGB (fancy: planes) out
-            fancy ? blocks * 128 + pd.pixels * 3 : 0.0};       // k_colour_fancy: planes in, RGB out
+            blocks * 8 + entries * 2 + (fancy ? blocks * 128 : pd.pixels * pd.out_px_bytes),  // k_idct_color: coefficients
+                                                                                 // in, the output's bytes (fancy: planes) out
+            fancy ? blocks * 128 + pd.pixels * pd.out_px_bytes : 0.0};  // k_colour_fancy: planes in, output out
         for (int k = 0; k < JD_NUM_KERNELS; k++) {
             if (k == 10 && !fancy) continue;  // k_colour_fancy runs only with the flag
             S.launches[k]++;
@@ -1311,6 +1330,7 @@ const char* jd_kernel_name(int k) {
 jd_status jd_ctx_create(jd_ctx** out, int hip_device, const jd_opts* opts) {
     if (!out) return JD_ERR_INVALID_ARG;
     *out = nullptr;
+    if (opts && !out_flags_valid(opts->flags)) return JD_ERR_INVALID_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || hip_device < 0 || hip_device >= ndev) return JD_ERR_INVALID_ARG;
     jd_ctx* ctx = new jd_ctx();
@@ -1569,6 +1589,12 @@ jd_status jd_decode(jd_ctx* ctx, const uint8_t* jpeg, size_t len, uint8_t* rgb, 
     return jd_status(r.status);
 }
 
+jd_status jd_output_bytes(const jd_header* hdr, unsigned flags, size_t* bytes) {
+    if (!hdr || !bytes || !out_flags_valid(flags) || hdr->width <= 0 || hdr->height <= 0) return JD_ERR_INVALID_ARG;
+    *bytes = out_bytes_of(*hdr, flags & kOutFlags);
+    return JD_OK;
+}
+
 jd_status jd_decode_file(jd_ctx* ctx, const char* path, uint8_t* rgb, size_t rgb_capacity, int rgb_on_device,
                          int* width, int* height) {
     if (!ctx || !path) return JD_ERR_INVALID_ARG;
@@ -1585,7 +1611,7 @@ jd_status jd_decode_file(jd_ctx* ctx, const char* path, uint8_t* rgb, size_t rgb
     if (width) *width = h.width;
     if (height) *height = h.height;
     if (!rgb) return JD_OK;  // header query
-    if (rgb_capacity < size_t(h.width) * h.height * 3) return JD_ERR_CAPACITY;
+    if (rgb_capacity < out_bytes_of(h, ctx->flags)) return JD_ERR_CAPACITY;
     return jd_decode(ctx, data.data(), data.size(), rgb, rgb_on_device, width, height);
 }
 

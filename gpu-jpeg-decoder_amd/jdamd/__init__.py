@@ -35,8 +35,13 @@ JD_FLAG_FANCY_UPSAMPLING = 8
 JD_FLAG_FULL_PIECES = 16
 JD_FLAG_ASYNC_DEPTH2 = 32
 JD_FLAG_WORST_CASE_POOLS = 64
+JD_FLAG_OUT_PLANAR = 128
+JD_FLAG_OUT_BGR = 256
+JD_FLAG_OUT_GRAY = 512
+LAYOUTS = ("hwc", "chw")
+CHANNELS = ("rgb", "bgr", "gray")
 PATHS = {"auto": 0, "sync": JD_FLAG_FORCE_SYNC, "lanes": JD_FLAG_FORCE_LANES, "full": JD_FLAG_FULL_PIECES}
-JD_ABI_VERSION = 8
+JD_ABI_VERSION = 9
 JD_NUM_KERNELS = 11
 KERNEL_NAMES = ["k_scan", "k_index", "k_compact", "k_subplan", "k_piece", "k_redo", "k_chain",
                 "k_gather", "k_dc_pred", "k_idct_color", "k_colour_fancy"]
@@ -89,7 +94,7 @@ EXPORTED_SYMBOLS = [
     "jd_memcpy_h2d", "jd_memcpy_d2h", "jd_synchronize", "jd_get_stats", "jd_reset_stats",
     "jd_kernel_name", "jd_test_idct", "jd_test_idct_exact", "jd_test_color", "jd_debug_fetch", "jd_ctx_last_error",
     "jd_test_copy_peak", "jd_device_bytes", "jd_host_register", "jd_host_unregister",
-    "jd_host_alloc", "jd_host_free",
+    "jd_host_alloc", "jd_host_free", "jd_output_bytes",
 ]
 
 _lib = None
@@ -146,6 +151,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         "jd_host_unregister": (c_int, [c_void_p, c_void_p]),
         "jd_host_alloc": (c_int, [c_void_p, c_size_t, ctypes.POINTER(c_void_p)]),
         "jd_host_free": (c_int, [c_void_p, c_void_p]),
+        "jd_output_bytes": (c_int, [ctypes.POINTER(_Header), ctypes.c_uint, ctypes.POINTER(c_size_t)]),
     }
     # an A/B build from an older tree may lack newer entry points: tolerated only on explicit opt-in
     experiment = p != LIB_PATH and _abi_mismatch_allowed()
@@ -194,6 +200,39 @@ def parse(data: bytes) -> Header:
         raise JDError(st, "jd_parse")
     return Header(h.width, h.height, h.ncomp, list(h.h), list(h.v), list(h.tq), h.hmax, h.vmax, h.mcux, h.mcuy,
                   h.blocks_per_mcu, h.restart_interval, h.subsampling, h.ecs_offset)
+
+
+def _c_header(hdr: Header) -> _Header:
+    h = _Header()
+    for f in ("width", "height", "ncomp", "hmax", "vmax", "mcux", "mcuy", "blocks_per_mcu", "restart_interval",
+              "subsampling", "ecs_offset"):
+        setattr(h, f, getattr(hdr, f))
+    for f in ("h", "v", "tq"):
+        for i, x in enumerate(getattr(hdr, f)):
+            getattr(h, f)[i] = x
+    return h
+
+
+def output_bytes(header: Header, flags: int = 0) -> int:
+    """Bytes of one image's output under a context created with `flags` (jd_output_bytes): 3*W*H, or
+    W*H with JD_FLAG_OUT_GRAY.  Only the JD_FLAG_OUT_* bits are looked at."""
+    n = ctypes.c_size_t()
+    h = _c_header(header)
+    st = load_library().jd_output_bytes(ctypes.byref(h), flags, ctypes.byref(n))
+    if st != JD_OK:
+        raise JDError(st, "jd_output_bytes")
+    return n.value
+
+
+def format_flags(layout: str = "hwc", channels: str = "rgb") -> int:
+    """The JD_FLAG_OUT_* bits of an output format.  ValueError for unknown values."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout: one of {LAYOUTS}, not {layout!r}")
+    if channels not in CHANNELS:
+        raise ValueError(f"channels: one of {CHANNELS}, not {channels!r}")
+    if channels == "gray":
+        return JD_FLAG_OUT_GRAY  # (with layout="chw": the single plane)
+    return (JD_FLAG_OUT_PLANAR if layout == "chw" else 0) | (JD_FLAG_OUT_BGR if channels == "bgr" else 0)
 
 
 def write_array(path: str, rgb: np.ndarray) -> None:
@@ -257,14 +296,21 @@ class Decoder:
     (cuda-decoder/src/parser.cu:324-358, 577-700) as a context object."""
 
     def __init__(self, device: int = 0, timing: bool = False, parse_threads: int = 0, path: str = "auto",
-                 fancy: bool = False, async_depth: int = 1, worst_case_pools: bool = False):
-        """fancy=True: libjpeg's triangular chroma upsampling instead of replication
+                 fancy: bool = False, async_depth: int = 1, worst_case_pools: bool = False, layout: str = "hwc",
+                 channels: str = "rgb"):
+        """layout="hwc" | "chw", channels="rgb" | "bgr" | "gray": the output format of every decode of
+        this Decoder (JD_FLAG_OUT_PLANAR / _BGR / _GRAY, see include/jd.h); output_shape() gives the
+        shape of an image's array.  channels="gray" is one [H, W] plane of the JPEG's luma under
+        either layout.
+        fancy=True: libjpeg's triangular chroma upsampling instead of replication
         (JD_FLAG_FANCY_UPSAMPLING; an option beyond the reference, see include/jd.h).
         async_depth=2: pipelined calls leave two batches in flight (JD_FLAG_ASYNC_DEPTH2).
         worst_case_pools=True: device pools sized for the densest stream the tables allow, so no
         image is ever decoded twice (JD_FLAG_WORST_CASE_POOLS; about twice the device memory)."""
         if async_depth not in (1, 2):
             raise ValueError("async_depth: 1 or 2")
+        self.format_flags = format_flags(layout, channels)  # ValueError before the library is touched
+        self.layout, self.channels = layout, channels
         self.lib = load_library()
         abi = self.lib.jd_abi_version()
         if abi != JD_ABI_VERSION:
@@ -275,7 +321,7 @@ class Decoder:
         self.ctx = ctypes.c_void_p()
         opts = _Opts((JD_FLAG_TIMING if timing else 0) | PATHS[path] | (JD_FLAG_FANCY_UPSAMPLING if fancy else 0) |
                      (JD_FLAG_ASYNC_DEPTH2 if async_depth == 2 else 0) |
-                     (JD_FLAG_WORST_CASE_POOLS if worst_case_pools else 0), parse_threads)
+                     (JD_FLAG_WORST_CASE_POOLS if worst_case_pools else 0) | self.format_flags, parse_threads)
         st = self.lib.jd_ctx_create(ctypes.byref(self.ctx), device, ctypes.byref(opts))
         if st != JD_OK:
             raise JDError(st, "jd_ctx_create")
@@ -298,11 +344,17 @@ class Decoder:
         except Exception:
             pass
 
+    def output_shape(self, height: int, width: int):
+        """Shape of a decoded image: (H, W, 3), (3, H, W) for layout="chw", (H, W) for channels="gray"."""
+        if self.channels == "gray":
+            return (height, width)
+        return (3, height, width) if self.layout == "chw" else (height, width, 3)
+
     # -- single image -----------------------------------------------------------------------
     def decode(self, data: bytes) -> np.ndarray:
-        """decode(bitstream) -> RGB uint8 [H, W, 3]."""
+        """decode(bitstream) -> uint8 array of output_shape() ([H, W, 3] RGB by default)."""
         hdr = parse(data)
-        out = np.empty((hdr.height, hdr.width, 3), np.uint8)
+        out = np.empty(self.output_shape(hdr.height, hdr.width), np.uint8)
         w, h = ctypes.c_int(), ctypes.c_int()
         st = self.lib.jd_decode(self.ctx, data, len(data), out.ctypes.data, 0, ctypes.byref(w), ctypes.byref(h))
         if st != JD_OK:
@@ -314,7 +366,7 @@ class Decoder:
         st = self.lib.jd_decode_file(self.ctx, path.encode(), None, 0, 0, ctypes.byref(w), ctypes.byref(h))
         if st != JD_OK:
             raise JDError(st, "jd_decode_file")
-        out = np.empty((h.value, w.value, 3), np.uint8)
+        out = np.empty(self.output_shape(h.value, w.value), np.uint8)
         st = self.lib.jd_decode_file(self.ctx, path.encode(), out.ctypes.data, out.nbytes, 0, ctypes.byref(w),
                                      ctypes.byref(h))
         if st != JD_OK:
@@ -334,7 +386,7 @@ class Decoder:
             keep.append(buf)
             try:
                 hdr = parse(d)
-                o = np.empty((hdr.height, hdr.width, 3), np.uint8)
+                o = np.empty(self.output_shape(hdr.height, hdr.width), np.uint8)
             except JDError:
                 o = None
             outs.append(o)

@@ -8,8 +8,10 @@
  * Each entry point below names the reference interface it replaces.  Everything is plain C:
  * pointers, sizes, status codes; no exceptions cross this boundary and no torch types appear.
  *
- * Output format: interleaved uint8 RGB, H*W*3 bytes, row-major (the reference writes the same
- * values as three int planes in a text `.array` file — jd_write_array reproduces that file).
+ * Output format: by default interleaved uint8 RGB, H*W*3 bytes, row-major (the reference writes the
+ * same values as three int planes in a text `.array` file — jd_write_array reproduces that file).
+ * A context may instead write planar, BGR or gray output (JD_FLAG_OUT_*, below); jd_output_bytes
+ * gives the size of an image's output in any of them.
  *
  * Threading: a jd_ctx belongs to one host thread and one HIP device.  Calls on one context are
  * ordered: the memcpy helpers and jd_synchronize run after every batch the context has launched
@@ -26,7 +28,7 @@
 extern "C" {
 #endif
 
-#define JD_ABI_VERSION 8
+#define JD_ABI_VERSION 9
 
 typedef enum jd_status {
     JD_OK = 0,
@@ -74,6 +76,25 @@ typedef struct jd_ctx jd_ctx;
  * launch, which precedes its collection). */
 #define JD_FLAG_WORST_CASE_POOLS 64u
 
+/* Output format of every decode of the context (fixed at jd_ctx_create, like the upsampling).  It
+ * is what is written at jd_item.rgb and the `rgb` arguments; jd_output_bytes gives its size.
+ *   (none)              interleaved RGB: out[(y*W + x)*3 + c], c = R, G, B
+ *   JD_FLAG_OUT_PLANAR  three dense planes: out[c*H*W + y*W + x], no padding between rows or planes
+ *   JD_FLAG_OUT_BGR     channel order B, G, R; combines with JD_FLAG_OUT_PLANAR
+ *   JD_FLAG_OUT_GRAY    one dense plane out[y*W + x] of luma, H*W bytes; combining it with either
+ *                       flag above is JD_ERR_INVALID_ARG
+ * Planar and BGR outputs hold exactly the bytes of the default decode, permuted: with replicate and
+ * with fancy upsampling, and for 1-component files (R = G = B).
+ * Gray is clamp(Y + 128, 0, 255), Y being the luma sample the replicate path colours: component
+ * 0's IDCT output clipped to [-256, 255], taken at [y*v0/vmax, x*h0/hmax].  For a 1-component file
+ * that is each channel of the default output; for a colour file it is the JPEG's own Y, not a
+ * function of the RGB bytes.  Gray never runs the fancy path: with JD_FLAG_FANCY_UPSAMPLING also set
+ * the context decodes gray exactly as without it (a luma plane below the maximum sampling factor is
+ * replicated); a defined extension like the others of DESIGN.md §2. */
+#define JD_FLAG_OUT_PLANAR 128u
+#define JD_FLAG_OUT_BGR 256u
+#define JD_FLAG_OUT_GRAY 512u
+
 typedef struct jd_opts {
     unsigned flags;
     int parse_threads; /* host parse workers for jd_decode_batch; 0 = auto (hardware threads) */
@@ -98,7 +119,8 @@ typedef struct jd_header {
 
 /* One batch item.  `jpeg` (host) is always required: headers are parsed on the host.
  * `jpeg_dev` may point at a device copy of the same bytes (already resident in HBM); when NULL the
- * library uploads the file itself.  `rgb` receives H*W*3 bytes; it is a device pointer when the
+ * library uploads the file itself.  `rgb` receives the image in the context's output format
+ * (jd_output_bytes: H*W*3 bytes, H*W for gray); it is a device pointer when the
  * batch call's rgb_on_device is non-zero, otherwise a host pointer. */
 typedef struct jd_item {
     const uint8_t* jpeg;
@@ -122,9 +144,15 @@ jd_status jd_ctx_destroy(jd_ctx* ctx);
  * (cuda-decoder/src/parser.cu:360-471, cpp-decoder/src/parser.cpp:24-103). */
 jd_status jd_parse(const uint8_t* jpeg, size_t len, jd_header* hdr);
 
+/* Bytes of one image's output under a context created with `flags`: 3*W*H, or W*H with
+ * JD_FLAG_OUT_GRAY.  Host, reentrant, context-free.  Only the JD_FLAG_OUT_* bits of flags are
+ * looked at; JD_ERR_INVALID_ARG for NULL arguments, gray combined with planar or BGR, or a header
+ * whose width or height is not positive. */
+jd_status jd_output_bytes(const jd_header* hdr, unsigned flags, size_t* bytes);
+
 /* decode(bitstream) -> RGB for one image.  Replaces extract()+decodeKernel<<<1,T>>>+write's D2H
  * (cuda-decoder/main.cu:7-40, parser.cu:577-611) and JPEGParser::extract()+decode()
- * (cpp-decoder/src/parser.cpp:24-195).  rgb must hold H*W*3 bytes. */
+ * (cpp-decoder/src/parser.cpp:24-195).  rgb must hold jd_output_bytes() bytes (H*W*3 by default). */
 jd_status jd_decode(jd_ctx* ctx, const uint8_t* jpeg, size_t len, uint8_t* rgb, int rgb_on_device,
                     int* width, int* height);
 
@@ -176,7 +204,8 @@ jd_status jd_host_unregister(jd_ctx* ctx, void* ptr);
 jd_status jd_host_alloc(jd_ctx* ctx, size_t bytes, void** ptr);
 jd_status jd_host_free(jd_ctx* ctx, void* ptr);
 
-/* `.array` text writer: "H W\n", then R, G, B planes as space-terminated decimal ints, one plane
+/* The writers below take interleaved RGB whatever the context's output format.
+ * `.array` text writer: "H W\n", then R, G, B planes as space-terminated decimal ints, one plane
  * per line, no trailing newline.  Replaces JPEGParser::write() (cpp-decoder/src/parser.cpp:197-209)
  * and the CUDA write() (cuda-decoder/src/parser.cu:702-744). */
 jd_status jd_write_array(const char* path, const uint8_t* rgb, int width, int height);

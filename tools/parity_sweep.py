@@ -9,12 +9,14 @@ optimised per-image Huffman tables; Pillow has no 4:4:0) and, for about a fifth 
 the entropy-coded data, are decoded in one
 batch call on the GPU through each entropy-decode path of the library (default, "sync": 1024-bit
 pieces with most speculative starts failing, "lanes": one lane per restart interval, "full": the
-full-batch piece geometry whatever the batch size; --fancy: with libjpeg fancy upsampling) and compared
+full-batch piece geometry whatever the batch size; --fancy: with libjpeg fancy upsampling; --format: to a
+planar, BGR or gray output format) and compared
 with the oracle (oracle/jdoracle.c via oracle/jdoracle.py, in a process pool): per-image status, and
 the pixels when the oracle decodes the image.  Any difference is written to --out with the image's
 parameters and the run exits non-zero.  The oracle is the checker only; nothing here is timed.
 """
 import argparse
+import functools
 import hashlib
 import json
 import os
@@ -62,15 +64,17 @@ def make_image(args):
     return data
 
 
-def oracle_digest(data, fancy=False):
+def oracle_digest(data, fancy=False, fmt=None):
+    """fmt (--format): the oracle's pixels permuted to that output format, or (gray) the luma
+    reference rebuilt from the oracle's coefficients (tests/format_cases.py)."""
     import jdoracle
 
     st, ref = jdoracle.decode(data, fancy=fancy)
-    return st, (hashlib.sha256(ref.tobytes()).hexdigest() if st == 0 else None)
+    if st == 0 and fmt:
+        import format_cases
 
-
-def oracle_digest_fancy(data):
-    return oracle_digest(data, True)
+        ref = format_cases.stream_reference(data, fmt, fancy=fancy)
+    return st, (hashlib.sha256(np.ascontiguousarray(ref).tobytes()).hexdigest() if st == 0 else None)
 
 
 def draw(rng, seed, pil=False):
@@ -99,6 +103,8 @@ def main():
     ap.add_argument("--workers", type=int, default=12)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "sweep.json"))
     ap.add_argument("--fancy", action="store_true", help="libjpeg fancy upsampling (its oracle: jdoracle fancy=True)")
+    ap.add_argument("--format", choices=["chw", "bgr", "chw-bgr", "gray"], default=None,
+                    help="decode to this output format and compare with the permuted oracle output (gray: the luma reference)")
     ap.add_argument("--pil", action="store_true", help="also Pillow-encoded images (standard and optimised tables)")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
@@ -107,7 +113,10 @@ def main():
     # initialises the GPU: no worker is a fork of a process holding a HIP context
     pool = ProcessPoolExecutor(a.workers, mp_context=multiprocessing.get_context("forkserver"))
     list(pool.map(time.sleep, [0.2] * a.workers))
-    decs = {p: jdamd.Decoder(0, path=p, fancy=a.fancy) for p in paths}
+    layout, channels = {None: ("hwc", "rgb"), "chw": ("chw", "rgb"), "bgr": ("hwc", "bgr"), "chw-bgr": ("chw", "bgr"),
+                        "gray": ("hwc", "gray")}[a.format]
+    decs = {p: jdamd.Decoder(0, path=p, fancy=a.fancy, layout=layout, channels=channels) for p in paths}
+    digest = functools.partial(oracle_digest, fancy=a.fancy and a.format != "gray", fmt=a.format)  # (gray ignores fancy)
     t_end = time.time() + 60 * a.minutes
     n_img = n_ok = n_bad_status = 0
     fails = []
@@ -120,7 +129,7 @@ def main():
                 params.append(draw(rng, seed, a.pil))
                 seed += 1
             datas = list(pool.map(make_image, params, chunksize=4))
-            ref = list(pool.map(oracle_digest_fancy if a.fancy else oracle_digest, datas, chunksize=4))
+            ref = list(pool.map(digest, datas, chunksize=4))
             path = paths[it % len(paths)]
             outs, status = decs[path].decode_batch(datas)
             for p, d, o, s, (st, dig) in zip(params, datas, outs, status, ref):
@@ -141,7 +150,7 @@ def main():
     for d in decs.values():
         d.close()
     res = {"retried_images": retried, "images": n_img, "decoded_equal_or_checked": n_ok, "corrupt_status_checked": n_bad_status,
-           "batches": it, "mismatches": fails, "seed": a.seed, "minutes": a.minutes, "fancy": a.fancy, "pil": a.pil,
+           "batches": it, "mismatches": fails, "seed": a.seed, "minutes": a.minutes, "fancy": a.fancy, "pil": a.pil, "format": a.format,
            "paths": paths}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
